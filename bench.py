@@ -9,18 +9,27 @@ device sink. Streams are independent: with --gpus N the same 4096-stream dataset
 rank r decodes streams [r*4096/N, (r+1)*4096/N), no data-path collective); the decoded frames are gathered at the end of
 the timed region through the C ABI (ncclAllGather over RCCL when N > 1, D2H when N == 1).
 
-At N == 1 the same line also carries, as `points` (outside the timed region, each with its own context and clock):
+A plain run does only what the headline needs: set-up, warm-up, the --steps timed steps, the outputs when --dump-outputs DIR
+is given, and the JSON line. Everything else below is measured with --full only.
+
+--dump-outputs DIR writes the frames the timed path delivered for its last step (frames whose sample_end falls in the
+samples of that step) as DIR/frames.npy (float64, one row per frame: stream, tech, type, flags, phase, rate, start, end,
+length; rank 0's streams, sorted) and DIR/frame_payload.npy (float32, the payload bytes of those frames end to end, row
+order). Above 64 MB in all, a fixed seeded sample of the streams is written.
+
+With --full, at N == 1 the same line also carries, as `points` (outside the timed region, each with its own context and clock):
 BASELINE configs 2-4 (every bundled capture as one stream), config 5 with sparse and with no traffic, one long stream, the
 share of config 5 one of eight GPUs holds, set S2 (off the capture grid: rotated IQ + noise), the same share fed from host
 memory (H2D included), and the round-1/2 headline (131072 streams x 8192-sample buffers: the sequential kernel's
 saturating point).
 
 Extra objects on the JSON line:
-  roofline         HBM roofline of the dominant kernel of the headline (nfc_wave_kernel, all its launches of a step)
-  roofline_search  the same for the scan kernel (the per-sample search kernel of the time-parallel path), measured on the
-                   config-5 point without traffic; `on_sparse_traffic`: on the sparse point
-  cpu_baseline     the reference's own lab::NfcDecoder (oracle/_ref/libnfcref.so) on this box's host cores on a bounded
-                   sample of the headline streams; the same leg checks GPU frames against the reference bit for bit
+  roofline         HBM roofline of the dominant kernel of the headline (nfc_wave_kernel, all its launches of a step); its
+                   measured streaming-read peak (a run of its own) with --full only
+  roofline_search  (--full) the same for the scan kernel (the per-sample search kernel of the time-parallel path), measured
+                   on the config-5 point without traffic; `on_sparse_traffic`: on the sparse point
+  cpu_baseline     (--full) the reference's own lab::NfcDecoder (oracle/_ref/libnfcref.so) on this box's host cores on a
+                   bounded sample of the headline streams; the same leg checks GPU frames against the reference bit for bit
 """
 import argparse
 import ctypes
@@ -149,6 +158,58 @@ def clamp_used(cursor, dropped, capacity):
     return min(cursor, limit) if dropped else min(cursor, capacity)
 
 
+def record_starts(words, used):
+    """word offsets of the records of a packed frame sink (frames.py layout: 9 header words, then (length + 3) // 4 payload
+    words); the same walk as frames.parse_sink without building the tuples (millions of frames on the headline)"""
+    import numpy as np
+    w = np.asarray(words)[:used]
+    if w.size < 9:
+        return np.zeros(0, dtype=np.int64)
+    size = 9 + ((w[8:].astype(np.int64) & 0xFFFFFFFF) + 3) // 4  # record size, were a record to start at this word
+    starts, pos = [], 0
+    while pos + 9 <= used:
+        starts.append(pos)
+        pos += int(size[pos])
+    return np.array(starts, dtype=np.int64)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_frames(out_dir, words, starts, first, n_streams, end_from, end_to, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the frames of the sink whose sample_end lies in [end_from, end_to) as out_dir/frames.npy (float64 rows:
+    stream - first, tech, type, flags, phase, rate, start, end, length; sorted by stream, start, end, then the rest) and
+    out_dir/frame_payload.npy (float32: the payload bytes of those rows end to end). Above `limit` bytes, the streams of a
+    fixed seeded permutation are kept while they fit. Returns what was written, for the JSON line."""
+    import numpy as np
+    w = np.ascontiguousarray(np.asarray(words), dtype=np.int32)
+    end = w[starts + 7].astype(np.int64) & 0xFFFFFFFF
+    at = starts[(end >= end_from) & (end < end_to)]
+    hdr = w[at[:, None] + np.arange(9)].astype(np.int64) & 0xFFFFFFFF
+    hdr[:, 0] -= first
+    row_bytes = 9 * 8 + 4 * hdr[:, 8]
+    sampled = int(row_bytes.sum()) > limit
+    if sampled:
+        per_stream = np.bincount(hdr[:, 0], weights=row_bytes, minlength=n_streams)
+        perm = np.random.default_rng(20261016).permutation(n_streams)
+        chosen = perm[np.cumsum(per_stream[perm]) <= limit]
+        keep = np.isin(hdr[:, 0], chosen)
+        hdr, at = hdr[keep], at[keep]
+    order = np.lexsort((hdr[:, 8], hdr[:, 5], hdr[:, 4], hdr[:, 3], hdr[:, 2], hdr[:, 1], hdr[:, 7], hdr[:, 6], hdr[:, 0]))
+    hdr, at = hdr[order], at[order]
+    nw = (hdr[:, 8] + 3) // 4
+    base = np.cumsum(nw) - nw  # first payload word of each row among all rows' payload words
+    idx = np.arange(int(nw.sum())) + np.repeat(at + 9 - base, nw)
+    raw = w[idx].view(np.uint8)
+    within = np.arange(raw.size) - np.repeat(4 * base, 4 * nw)
+    payload = raw[within < np.repeat(hdr[:, 8], 4 * nw)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frames.npy"), hdr.astype(np.float64).reshape(-1, 9))
+    np.save(os.path.join(out_dir, "frame_payload.npy"), payload.astype(np.float32))
+    return {"dir": out_dir, "frames": int(hdr.shape[0]), "payload_bytes": int(payload.size), "streams": int(np.unique(hdr[:, 0]).size),
+            "sampled_streams": sampled, "sample_end_range": [int(end_from), int(end_to)]}
+
+
 def headline_layout(steps, warmup, samples, slices):
     """(slices resident, samples per stream resident) of the headline dataset: SURVEY 8(d) fixes it at L samples per stream
     (32 GiB for 4096 streams x 2^20) so that the identical data serves every run; `slices` of them are kept (default 2) and
@@ -193,9 +254,14 @@ def main():
     ap.add_argument("--allow-torch-gather", action="store_true",
                     help="N > 1: should the C ABI's RCCL communicator not come up on every rank, measure the line with torch.distributed's "
                          "all_gather instead (and say so in config.parallelism) rather than fail. Default: the product's gather or an error")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-points", action="store_true", help="headline only")
-    ap.add_argument("--points-budget", type=float, default=780.0, help="no new point is started later than this many seconds after the start")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and its parity check against the reference, "
+                         "the points (BASELINE's other configurations), roofline_search and the measured streaming-read peak")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames of the last step as DIR/frames.npy and DIR/frame_payload.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) without the CPU baseline and parity leg")
+    ap.add_argument("--no-points", action="store_true", help="(--full) without the points")
+    ap.add_argument("--points-budget", type=float, default=420.0, help="no new point is started later than this many seconds after the start")
     ap.add_argument("--points", default="fixtures_single,config5_sparse,config5_idle,share_sparse,share_dense,share_dense_h2d,single_sparse,single_dense,s2_share,s2_config5,saturating")
     ap.add_argument("--saturating-streams", type=int, default=131072, help="streams of the `saturating` point (8192-sample buffers, sequential kernel)")
     ap.add_argument("--share-streams", type=int, default=512, help="streams one GPU holds when BASELINE's 4096 are spread over 8")
@@ -377,8 +443,8 @@ def main():
     busy_ms = wave_busy_ms if dominant == "nfc_wave_kernel" else kernel_ms
     achieved_busy = bytes_per_launch / (busy_ms * 1e-3) / 1e9 if busy_ms > 0 else 0.0
 
-    # the measured denominator: streaming read of this very buffer with 16-byte loads
-    read_peak = 0.0 if dry else gpu.read_bandwidth(data.data_ptr(), min(data.numel() * 4, 32 << 30), repeats=5)
+    # the measured denominator: streaming read of this very buffer with 16-byte loads (a run of its own: --full)
+    read_peak = gpu.read_bandwidth(data.data_ptr(), min(data.numel() * 4, 32 << 30), repeats=5) if args.full and not dry else 0.0
 
     traffic, traffic_source = stored_traffic(dominant, S, L)
     traffic_step, traffic_step_source = stored_traffic("step", S, L)  # every kernel of a step, not only the dominant one
@@ -434,7 +500,7 @@ def main():
                             "library's two streams may overlap, so this is a sum of launch durations, not exclusive time)",
             "kernel_launches_per_step": round((st.wave_launches if dominant == "nfc_wave_kernel" else st.launches) / K, 1),
             "algorithmic_bytes_per_launch": bytes_per_launch,
-            "peak_measured_streaming_read": round(read_peak, 1),
+            "peak_measured_streaming_read": round(read_peak, 1) if read_peak > 0 else None,
             "frac_of_measured_peak": round(achieved / read_peak, 6) if read_peak > 0 else None,
             "kernel_busy_ms": round(busy_ms, 4),
             "kernel_busy_ms_is": "time per step during which the kernel was running at all: union of its launch intervals (HIP events against one epoch event)",
@@ -444,18 +510,24 @@ def main():
         "frames_dropped": dropped,
     }
 
-    frames = framelib.parse_sink(host_words, host_used, FS) if rank == 0 else {}
     if rank == 0:
-        result["config"]["frames_decoded_rank0"] = sum(len(v) for v in frames.values())
+        starts = record_starts(host_words, host_used)
+        result["config"]["frames_decoded_rank0"] = int(starts.size)
         result["config"]["frame_words_gathered"] = int(total_words)
+        if args.dump_outputs:
+            # the last step submitted samples [(W + K - 1) L, (W + K) L) of every stream
+            result["outputs"] = dump_frames(args.dump_outputs, host_words, starts, first, S, (W + K - 1) * L, (W + K) * L)
 
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import nfc_testlib as TL
-    lib = TL.reference_lib() if rank == 0 else None
+    lib = None
+    if args.full and rank == 0:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import nfc_testlib as TL
+        lib = TL.reference_lib()
 
-    # ---- CPU baseline + parity check against the real reference (rank 0, N == 1 only) ----
-    if rank == 0 and world == 1 and not args.no_cpu:
+    # ---- (--full) CPU baseline + parity check against the real reference (rank 0, N == 1 only) ----
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         if lib is not None:
+            frames = framelib.parse_sink(host_words, host_used, FS)
             C = min(S, args.cpu_streams)
             # what the decoder saw: slice order[k] of the resident data in step k. The CPU legs are bounded (about
             # 10-30 s of CPU work): the timing leg takes the first min(K + W, 3) steps of C streams, the parity leg the whole
@@ -627,8 +699,8 @@ def main():
     del data
     torch.cuda.empty_cache()
 
-    # ---- BASELINE's own configurations (N == 1): each point on its own context and clock, outside the headline's timed region ----
-    if rank == 0 and world == 1 and not args.no_points:
+    # ---- (--full) BASELINE's own configurations (N == 1): each point on its own context and clock, outside the headline's timed region ----
+    if args.full and rank == 0 and world == 1 and not args.no_points:
         segs = synth.sparse_segments(template)
         points = {}
         point_sink_words = 64 << 20  # (a point is at most 8 submissions)

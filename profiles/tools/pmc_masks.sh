@@ -6,7 +6,7 @@ root=$(pwd)
 out=$root/gpurun_out/masks
 mkdir -p $out
 for mask in 0 1 2 4 8 15; do
-  (cd /tmp && NFC_BENCH_IDLE=${MASKS_IDLE:-1} NFC_BENCH_TECH_MASK=$mask rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_WAVES -d $out/m$mask -o run --output-format csv -- python $root/bench.py --streams 131072 --steps 2 --warmup 1 --no-cpu > $out/m$mask.log 2>&1)
+  (cd /tmp && NFC_BENCH_IDLE=${MASKS_IDLE:-1} NFC_BENCH_TECH_MASK=$mask rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_WAVES -d $out/m$mask -o run --output-format csv -- python $root/bench.py --full --streams 131072 --steps 2 --warmup 1 --no-cpu > $out/m$mask.log 2>&1)
   python $root/profiles/tools/summarize_pmc.py $out/m$mask > $out/m$mask.json
   python - <<PY
 import json

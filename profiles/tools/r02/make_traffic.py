@@ -35,7 +35,7 @@ def main():
         calib[c] = CAL_BYTES / (vals[-1] * 1024.0) if vals else None
 
     result = {"round": 2, "command": "profiles/tools/r02/round_profile.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, separately, WRITE_SIZE) -- "
-                                      "python bench.py --no-cpu --steps 2 --warmup 1 --points config5_idle; no other trace domains",
+                                      "python bench.py --full --no-cpu --steps 2 --warmup 1 --points config5_idle; no other trace domains",
               "calibration": {"tool": "profiles/tools/calib_traffic.hip (8 GiB read, 8 GiB written)", "fetch_size_factor": calib["FETCH_SIZE"],
                               "write_size_factor": calib["WRITE_SIZE"]}, "kernels": {}}
 

@@ -14,7 +14,7 @@ out=$root/gpurun_out/$tag
 mkdir -p $out
 cd $root
 
-python bench.py > $out/bench_n1.json 2> $out/bench_n1.err
+python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err
 
 # headline only: nfc_demod_fixed_kernel's average here is the launch time of roofline.kernel_ms_avg (first launch of every stream
 # runs the exact-modulo variant, the warm-up launches are in the average too)
@@ -22,12 +22,12 @@ python bench.py > $out/bench_n1.json 2> $out/bench_n1.err
 cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/rocprofv3_kernel_stats.csv 2>/dev/null
 cp $(find $out/trace -name "*domain_stats.csv" | head -1) $out/rocprofv3_domain_stats.csv 2>/dev/null
 # the points that exercise the time-parallel path (idle: nfc_scan_kernel = roofline_search; sparse: the windowed decode)
-(cd /tmp && rocprofv3 --kernel-trace --stats -d $out/trace_points -o run --output-format csv -- python $root/bench.py --no-cpu --steps 1 --warmup 1 --points config5_idle,config5_sparse,single_sparse > $out/trace_points.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats -d $out/trace_points -o run --output-format csv -- python $root/bench.py --full --no-cpu --steps 1 --warmup 1 --points config5_idle,config5_sparse,single_sparse > $out/trace_points.log 2>&1)
 cp $(find $out/trace_points -name "*kernel_stats.csv" | head -1) $out/rocprofv3_kernel_stats_points.csv 2>/dev/null
 
 hipcc --offload-arch=gfx950 -O2 profiles/tools/calib_traffic.hip -o /tmp/calib_traffic
 for c in FETCH_SIZE WRITE_SIZE; do
-  (cd /tmp && rocprofv3 --kernel-trace --pmc $c -d $out/pmc_$c -o run --output-format csv -- python $root/bench.py --no-cpu --steps 2 --warmup 1 --points config5_idle > $out/pmc_$c.log 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --pmc $c -d $out/pmc_$c -o run --output-format csv -- python $root/bench.py --full --no-cpu --steps 2 --warmup 1 --points config5_idle > $out/pmc_$c.log 2>&1)
   (cd /tmp && rocprofv3 --kernel-trace --pmc $c -d $out/calib_$c -o run --output-format csv -- /tmp/calib_traffic > $out/calib_$c.log 2>&1)
 done
 python profiles/tools/summarize_pmc.py $out/trace > $out/kernel_trace_summary.json

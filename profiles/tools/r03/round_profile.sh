@@ -15,7 +15,7 @@ out=$root/gpurun_out/$tag
 mkdir -p $out
 cd $root
 
-python bench.py > $out/bench_n1.json 2> $out/bench_n1.err
+python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err
 
 head="python $root/bench.py --no-cpu --no-points --steps 1 --warmup 1"
 (cd /tmp && rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python $root/bench.py --no-cpu --no-points > $out/trace.log 2>&1)

@@ -14,7 +14,7 @@ except Exception as e:
     print("%-10s no line: %s" % ("$1", e))
 PY
 }
-timeout 70 python bench.py --steps 4 --warmup 1 --no-points > $OUT/on.json 2> $OUT/on.err; line on
+timeout 70 python bench.py --full --steps 4 --warmup 1 --no-points > $OUT/on.json 2> $OUT/on.err; line on
 NFCGPU_ENVELOPE_KERNEL=0 timeout 40 python bench.py --steps 4 --warmup 1 --no-points --no-cpu > $OUT/off.json 2> $OUT/off.err; line off
 for k in 1 0; do
    echo "== NFCGPU_ENVELOPE_KERNEL=$k" | tee -a $OUT/times.txt

@@ -9,7 +9,7 @@ PKG=nfc-laboratory_amd
 run() { # name, library, timeout, extra flags
    local name=$1 lib=$2 limit=$3; shift 3
    local t0=$SECONDS
-   NFCGPU_LIB=$lib timeout $limit python bench.py --steps 4 --warmup 1 --no-points "$@" > $OUT/$name.json 2> $OUT/$name.err
+   NFCGPU_LIB=$lib timeout $limit python bench.py --full --steps 4 --warmup 1 --no-points "$@" > $OUT/$name.json 2> $OUT/$name.err
    echo "$name rc=$? $((SECONDS - t0)) s" | tee -a $OUT/times.txt
    python - <<PY | tee -a $OUT/times.txt
 import json

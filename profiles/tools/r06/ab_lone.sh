@@ -9,7 +9,7 @@ OUT=gpurun_out/r06_lone
 mkdir -p $OUT
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { echo build failed; tail -20 $OUT/build.log; exit 1; }
 for lone in 0 1024; do
-   NFCGPU_LONE_LANES=$lone timeout 900 python bench.py --steps 6 --warmup 2 --no-cpu --points fixtures_single,share_dense,single_dense \
+   NFCGPU_LONE_LANES=$lone timeout 900 python bench.py --full --steps 6 --warmup 2 --no-cpu --points fixtures_single,share_dense,single_dense \
       > $OUT/bench_lone$lone.json 2> $OUT/bench_lone$lone.err
    echo "lone=$lone rc=$?"
    python - $OUT/bench_lone$lone.json <<'PY'

@@ -12,7 +12,7 @@ python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { ec
 for round in 1 2; do
 for lib in "$@"; do
    name=$(basename $lib .so)
-   NFCGPU_LIB=$PWD/nfc-laboratory_amd/$lib timeout 900 python bench.py --steps 6 --warmup 2 --no-cpu --points $POINTS \
+   NFCGPU_LIB=$PWD/nfc-laboratory_amd/$lib timeout 900 python bench.py --full --steps 6 --warmup 2 --no-cpu --points $POINTS \
       > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err
    echo "$name round $round rc=$?"
    python - $OUT/bench_${name}_$round.json <<'PY'

@@ -33,7 +33,7 @@ done
 
 # 2b. the sequential kernel's traffic on the sources as they are (its record was round 2's): the `saturating`
 #     point of the bench (131072 streams x 8192-sample buffers) behind a small headline
-seq="python $root/bench.py --no-cpu --steps 1 --warmup 1 --streams 64 --samples 65536 --points saturating"
+seq="python $root/bench.py --full --no-cpu --steps 1 --warmup 1 --streams 64 --samples 65536 --points saturating"
 for c in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $c -d $out/seq_$c -o run --output-format csv -- $seq > $out/seq_$c.log 2>&1)
 done

@@ -51,3 +51,40 @@ def test_the_headline_of_the_drivers_command_fits_the_gpu():
     assert bench.headline_sink_words(512, 1 << 20, 2, 1) >= 16 << 20
     # N ranks under strong scaling: every rank's share plus a gather buffer for all of them
     assert bench.headline_device_bytes(512, 1 << 20, 20, 5, world=8) < 40 * gib
+
+
+def test_dumped_frames_are_the_last_steps_frames_of_the_sink(tmp_path):
+    """--dump-outputs: the records of the sink whose sample_end falls in the last step, every field and payload byte as
+    frames.parse_sink reads them, sorted by stream and time; above the size limit a seeded sample of whole streams"""
+    import numpy as np
+    import frames as framelib
+    rng = np.random.default_rng(7)
+    first, fs = 100, 10000000
+    recs = {}
+    for s in range(40):
+        recs[first + s] = [(int(rng.integers(1, 5)), 0x102, 0, 0, 106, int(a), int(a) + int(rng.integers(1, 500)), fs,
+                            bytes(rng.integers(0, 256, int(rng.integers(0, 40))).astype(np.uint8))) for a in rng.integers(0, 300000, 30)]
+    words = framelib.pack_frames(recs)
+    starts = bench.record_starts(words, words.size)
+    parsed = framelib.parse_sink(words, words.size, fs)
+    assert starts.size == sum(len(v) for v in parsed.values()) == 40 * 30
+    want = sorted(((sid - first,) + f for sid, v in parsed.items() for f in v if 100000 <= f[6] < 200000),
+                  key=lambda t: (t[0], t[6], t[7], t[1], t[2], t[3], t[4], t[5], len(t[9])))
+    for limit in (bench.DUMP_LIMIT_BYTES, 4000):
+        out = tmp_path / str(limit)
+        info = bench.dump_frames(str(out), words, starts, first, 40, 100000, 200000, limit=limit)
+        rows, payload = np.load(out / "frames.npy"), np.load(out / "frame_payload.npy")
+        assert rows.dtype == np.float64 and rows.shape[1] == 9 and payload.dtype == np.float32
+        got, at = [], 0
+        for r in rows.astype(np.int64):
+            got.append((int(r[0]),) + tuple(int(v) for v in r[1:8]) + (fs, bytes(payload[at:at + r[8]].astype(np.uint8))))
+            at += int(r[8])
+        assert at == payload.size and info["frames"] == len(got)
+        kept = set(int(v) for v in rows[:, 0])
+        assert got == [t for t in want if t[0] in kept]
+        if limit == bench.DUMP_LIMIT_BYTES:
+            assert not info["sampled_streams"] and len(got) == len(want)
+        else:
+            assert info["sampled_streams"] and 0 < len(kept) < 40 and rows.size * 8 + payload.size * 4 <= limit
+            again = bench.dump_frames(str(tmp_path / "again"), words, starts, first, 40, 100000, 200000, limit=limit)
+            assert again["frames"] == info["frames"] and np.array_equal(np.load(tmp_path / "again" / "frames.npy"), rows)
