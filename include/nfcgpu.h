@@ -192,6 +192,50 @@ int nfcgpu_magnitude(nfcgpu_ctx *ctx, const float *iq, uint64_t n_samples, float
 int nfcgpu_resample_radio(nfcgpu_ctx *ctx, const float *in, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_samples,
                           float *out, uint64_t out_pitch_bytes, uint32_t capacity_pairs, uint32_t *counts, uint32_t location);
 
+/* Spectrum of interleaved float IQ for display: what the reference's FourierProcessTask, the consumer of "radio.signal.iq",
+ * publishes on "signal.fft" (lab-tasks/src/main/cpp/tasks/FourierProcessTask.cpp, the SSE2 branches that
+ * lab-tasks/CMakeLists.txt:18 builds), for every frame of every buffer instead of one buffer every 10 ms:
+ *   - length 1024, window "Hamming", bandwidth 625 000 Hz (:45-49, :86); decimation D = int(sample rate / bandwidth) (:239),
+ *     16 at 10 MS/s; a buffer with fewer than L * D elements gives nothing (:242);
+ *   - window tables (:121-143) under the reference's names, which are not what they compute: "Hamming" is
+ *     float(pow(sin(float(M_PI * n / L)), 2)), a periodic Hann; "Hann" is float(0.5 * (1.0 - cos(2.0 * M_PI * n / (L - 1)))),
+ *     the symmetric one; anything else is 1;
+ *   - input (:250-262): eight floats out of every 8 D, times the window in fp32: FFT input m is the source pair
+ *     4 * D * (m >> 2) + (m & 3), four consecutive pairs out of every 4 D, not every D-th pair;
+ *   - forward complex FFT, unnormalised (:276); sqrtf(re * re + im * im), products and sum rounded separately (:279-341);
+ *   - L floats per frame with the halves swapped: bins L/2 ... L-1 (negative frequencies) first, then 0 ... L/2-1 (:344-348).
+ * Window product and magnitude are the reference's operations to the bit; the butterflies are this library's own (the
+ * reference's are mufft's), so values agree with the reference's to the rounding error of a float FFT, not bit for bit. */
+#define NFCGPU_WINDOW_NONE 0
+#define NFCGPU_WINDOW_HAMMING 1
+#define NFCGPU_WINDOW_HANN 2
+
+typedef struct nfcgpu_spectrum_params {
+   uint32_t length;      /* FFT length L, a power of two, 256 ... 4096; the reference's is 1024 */
+   uint32_t window;      /* NFCGPU_WINDOW_NONE 0, NFCGPU_WINDOW_HAMMING 1 (the reference's default), NFCGPU_WINDOW_HANN 2:
+                            the reference's tables under the reference's names (see above for what they compute) */
+   uint32_t decimation;  /* D >= 1; 0 = derive it as the reference does, sample_rate / 625000 (at least 1) */
+   uint32_t hop;         /* IQ pairs between the starts of successive frames of one buffer; 0 = one frame at pair 0,
+                            which is what FourierProcessTask publishes for that buffer */
+   uint32_t sample_rate; /* used only when decimation == 0 */
+   uint32_t reserved[3]; /* zero */
+} nfcgpu_spectrum_params;
+
+void nfcgpu_spectrum_default_params(nfcgpu_spectrum_params *p);   /* 1024, HAMMING, 0, 0, 10000000 */
+
+/* frames a buffer of n_pairs IQ pairs gives: 0 if n_pairs < L*D (the reference's guard, FourierProcessTask.cpp:242), else 1
+ * for hop == 0, else (n_pairs - L*D) / hop + 1. 0 also for parameters nfcgpu_spectrum refuses. */
+uint32_t nfcgpu_spectrum_frames(const nfcgpu_spectrum_params *p, uint32_t n_pairs);
+
+/* Buffer b is n_pairs interleaved IQ pairs at iq + b * in_pitch_bytes (8-byte aligned, in_pitch_bytes a multiple of 8); its
+ * frames f = 0 ... frames-1 start at pair f * hop and are written as L floats each, in the reference's order, at
+ * out + b * out_pitch_bytes + f * L * 4 (out_pitch_bytes a multiple of 16 and at least frames * L * 4;
+ * bytes of a pitch beyond the frames are left alone). One launch transforms all n_buffers * frames frames
+ * (FourierProcessTask::process(), :236-355, is one frame). `location` applies to `iq` and `out`; the call returns when `out`
+ * is complete. Zero frames is success and writes nothing. */
+int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_pairs,
+                    const nfcgpu_spectrum_params *params, float *out, uint64_t out_pitch_bytes, uint32_t location);
+
 /* nextFrames(invalid buffer) (NfcDecoder.cpp:449-463): queues one carrier-state frame stamped with the stream's clock */
 int nfcgpu_flush(nfcgpu_ctx *ctx, uint32_t stream_id);
 /* waits for everything submitted, then moves the frames of the frame sink to the per-stream queues. poll / pending /

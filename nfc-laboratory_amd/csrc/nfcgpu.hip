@@ -11,6 +11,7 @@
 #include <dlfcn.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +25,7 @@
 #include "nfc_config.hpp"
 #include "nfc_launch.h"
 #include "nfc_scan_launch.h"
+#include "nfc_spectrum.hpp"
 
 __global__ void nfc_demod_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
 __global__ void nfc_demod_exact_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
@@ -52,6 +54,45 @@ __global__ void nfc_scan_planes_kernel(const NfcConfig *__restrict__ cfgPtr, Nfc
 __global__ void nfc_envelope_kernel(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A);
 __global__ void nfc_wave_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L, NfcScanArgs A, uint32_t mode);
 __global__ void nfc_planes_stale_kernel(NfcScanArgs A, const NfcScanChunk *all, uint32_t nAll, NfcScanChunk *out, uint32_t *count);
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+/* The test build's twins of the spectrum kernels (nfc_spectrum.hip): the same steps from nfc_spectrum.hpp, the grid, the
+ * steps and the threads of a workgroup as loops, the end of a loop over the threads where the device has a barrier. */
+namespace {
+
+template <int L, int STEP>
+void spectrum_twin_steps(const NfcSpectrumArgs &A, uint64_t frame, NfcSpectrumRegs<L> *regs, float *ldsRe, float *ldsIm)
+{
+   for (int lane = 0; lane < NfcSpectrumShape<L>::kThreads; lane++)
+      nfc_spectrum_step<L, STEP>(A, frame, lane, regs[lane], ldsRe, ldsIm);
+
+   if constexpr (STEP + 1 < NfcSpectrumShape<L>::kSteps)
+      spectrum_twin_steps<L, STEP + 1>(A, frame, regs, ldsRe, ldsIm);
+}
+
+template <int L>
+void spectrum_twin(const NfcSpectrumArgs &A)
+{
+   static NfcSpectrumRegs<L> regs[NfcSpectrumShape<L>::kThreads];
+   static float ldsRe[NfcSpectrumShape<L>::kLdsFloats], ldsIm[NfcSpectrumShape<L>::kLdsFloats];
+
+   for (uint64_t block = 0; block < fakehip::launchGrid.x; block++)
+      for (uint64_t frame = block; frame < A.total; frame += fakehip::launchGrid.x)
+         spectrum_twin_steps<L, 0>(A, frame, regs, ldsRe, ldsIm);
+}
+
+}
+#define NFC_SPECTRUM_KERNEL(L) \
+   void nfc_spectrum_kernel_##L(NfcSpectrumArgs A) { spectrum_twin<L>(A); }
+#else
+#define NFC_SPECTRUM_KERNEL(L) __global__ void nfc_spectrum_kernel_##L(NfcSpectrumArgs A);
+#endif
+NFC_SPECTRUM_KERNEL(256)
+NFC_SPECTRUM_KERNEL(512)
+NFC_SPECTRUM_KERNEL(1024)
+NFC_SPECTRUM_KERNEL(2048)
+NFC_SPECTRUM_KERNEL(4096)
+#undef NFC_SPECTRUM_KERNEL
 
 namespace {
 
@@ -211,6 +252,13 @@ struct nfcgpu_ctx
    nfcgpu_stats stats {};
    std::string lastError;
 
+   /* nfcgpu_spectrum: window and twiddle tables on the device, one block per (length, window) used so far, kept */
+   struct SpectrumTables
+   {
+      uint32_t length = 0, window = 0;
+      float *d = nullptr; /* `length` window factors, then `length` twiddles (float2) */
+   };
+   std::vector<SpectrumTables> spectrumTables;
 };
 
 namespace {
@@ -2242,6 +2290,8 @@ int nfcgpu_shutdown(nfcgpu_ctx *ctx)
    (void)hipFree(ctx->ownSinkCtl ? ctx->ownSinkCtl : ctx->dSinkCtl);
    (void)hipFree(ctx->dWorks);
    (void)hipFree(ctx->dConfigs);
+   for (nfcgpu_ctx::SpectrumTables &t: ctx->spectrumTables)
+      (void)hipFree(t.d);
    for (nfcgpu_ctx::StageSlot &slot: ctx->stage)
    {
       if (slot.d)
@@ -2734,6 +2784,213 @@ int nfcgpu_resample_radio(nfcgpu_ctx *ctx, const float *in, uint64_t inPitch, ui
       if (hostCounts[b] > capacityPairs)
          return fail(ctx, NFCGPU_EOVERFLOW, "resampler output capacity exceeded: raise capacity_pairs");
    }
+
+   return NFCGPU_OK;
+}
+
+/* ---- nfcgpu_spectrum: FourierProcessTask::process() (FourierProcessTask.cpp:236-355) for every frame of every buffer ---- */
+
+/* what is wrong with the parameters, or nullptr; *decimation = the D in force */
+static const char *spectrum_check(const nfcgpu_spectrum_params *p, uint32_t *decimation)
+{
+   if (!p)
+      return "spectrum: params is NULL";
+   if (p->length < 256 || p->length > 4096 || (p->length & (p->length - 1)))
+      return "spectrum: length is not a power of two from 256 to 4096";
+   if (p->window > NFCGPU_WINDOW_HANN)
+      return "spectrum: unknown window";
+   if (p->reserved[0] || p->reserved[1] || p->reserved[2])
+      return "spectrum: reserved words are not zero";
+
+   /* decimation = int(sampleRate / bandwidth), bandwidth = 10E6 / 16 (FourierProcessTask.cpp:49, :239) */
+   uint32_t d = p->decimation ? p->decimation : p->sample_rate / 625000u;
+   *decimation = d ? d : 1;
+   return nullptr;
+}
+
+static uint32_t spectrum_frames(const nfcgpu_spectrum_params *p, uint32_t decimation, uint32_t nPairs)
+{
+   const uint64_t span = (uint64_t)p->length * decimation;
+   if (nPairs < span)
+      return 0; /* FourierProcessTask.cpp:242 */
+   return p->hop ? (uint32_t)((nPairs - span) / p->hop) + 1 : 1;
+}
+
+/* Window (FourierProcessTask.cpp:121-143, the reference's expressions in the reference's types: the sine of "Hamming" is taken of a
+ * float and is a float, its square is pow(double, 2)) and twiddles exp(-2 pi i n / L) in double, rounded once. */
+static int spectrum_tables(nfcgpu_ctx *ctx, uint32_t length, uint32_t window, const float **dWindow, const float2 **dTwiddle)
+{
+   for (const nfcgpu_ctx::SpectrumTables &t: ctx->spectrumTables)
+   {
+      if (t.length == length && t.window == window)
+      {
+         *dWindow = t.d;
+         *dTwiddle = (const float2 *)(t.d + length);
+         return NFCGPU_OK;
+      }
+   }
+
+   const int L = (int)length;
+   std::vector<float> host(3 * (size_t)length);
+
+   for (int n = 0; n < L; n++)
+   {
+      switch (window)
+      {
+         case NFCGPU_WINDOW_HAMMING:
+            host[n] = static_cast<float>(std::pow(std::sin(static_cast<float>(M_PI * n / L)), 2));
+            break;
+         case NFCGPU_WINDOW_HANN:
+            host[n] = static_cast<float>(0.5 * (1.0 - std::cos((2.0 * M_PI * n) / (L - 1))));
+            break;
+         default:
+            host[n] = 1;
+            break;
+      }
+
+      const double angle = -2.0 * M_PI * (double)n / (double)L;
+      host[length + 2 * n] = (float)std::cos(angle);
+      host[length + 2 * n + 1] = (float)std::sin(angle);
+   }
+
+   nfcgpu_ctx::SpectrumTables t;
+   t.length = length;
+   t.window = window;
+
+   if (hipMalloc((void **)&t.d, host.size() * sizeof(float)) != hipSuccess)
+      return fail(ctx, NFCGPU_ENOMEM, "spectrum tables allocation failed");
+
+   hipError_t err = hipMemcpy(t.d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+   if (err != hipSuccess)
+   {
+      (void)hipFree(t.d);
+      return fail(ctx, NFCGPU_EHIP, "hipMemcpy(H2D spectrum tables)", err);
+   }
+
+   ctx->spectrumTables.push_back(t);
+   *dWindow = t.d;
+   *dTwiddle = (const float2 *)(t.d + length);
+   return NFCGPU_OK;
+}
+
+void nfcgpu_spectrum_default_params(nfcgpu_spectrum_params *p)
+{
+   if (!p)
+      return;
+   std::memset(p, 0, sizeof(*p));
+   p->length = 1024;
+   p->window = NFCGPU_WINDOW_HAMMING;
+   p->sample_rate = 10000000;
+}
+
+uint32_t nfcgpu_spectrum_frames(const nfcgpu_spectrum_params *p, uint32_t nPairs)
+{
+   uint32_t decimation = 1;
+   if (spectrum_check(p, &decimation))
+      return 0;
+   return spectrum_frames(p, decimation, nPairs);
+}
+
+int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t nBuffers, uint32_t nPairs, const nfcgpu_spectrum_params *params,
+                    float *out, uint64_t outPitch, uint32_t location)
+{
+   if (!ctx)
+      return NFCGPU_EINVAL;
+
+   uint32_t decimation = 1;
+   if (const char *why = spectrum_check(params, &decimation))
+      return fail(ctx, NFCGPU_EINVAL, why);
+   if (!iq || ((uintptr_t)iq & 7))
+      return fail(ctx, NFCGPU_EINVAL, "spectrum: iq is NULL or not 8-byte aligned");
+   if (!out || ((uintptr_t)out & 3))
+      return fail(ctx, NFCGPU_EINVAL, "spectrum: out is NULL or not 4-byte aligned");
+   if (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE)
+      return fail(ctx, NFCGPU_EINVAL, "spectrum: unknown location");
+   if (inPitch & 7)
+      return fail(ctx, NFCGPU_EINVAL, "spectrum: in_pitch_bytes is not a multiple of 8");
+
+   const uint32_t L = params->length;
+   const uint32_t frames = spectrum_frames(params, decimation, nPairs);
+   const uint64_t rowBytes = (uint64_t)frames * L * 4;
+
+   if ((outPitch & 15) || outPitch < rowBytes)
+      return fail(ctx, NFCGPU_EINVAL, "spectrum: out_pitch_bytes is not a multiple of 16 or smaller than the frames of a buffer");
+   if (nBuffers == 0 || frames == 0)
+      return NFCGPU_OK;
+
+   HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+   NfcSpectrumArgs A;
+   std::memset(&A, 0, sizeof(A));
+
+   int rc = spectrum_tables(ctx, L, params->window, &A.window, &A.twiddle);
+   if (rc)
+      return rc;
+
+   uint8_t *scratch = nullptr;
+   /* what the buffers span: the pitch between them, the data of the last one */
+   const size_t inBytes = (size_t)inPitch * (nBuffers - 1) + (size_t)nPairs * 8, outBytes = (size_t)outPitch * (nBuffers - 1) + (size_t)rowBytes;
+
+   A.iq = (const float2 *)iq;
+   A.out = out;
+
+   if (location == NFCGPU_LOC_HOST)
+   {
+      /* one temporary device block: input, output (this entry point is not on the streaming path) */
+      if (hipMalloc((void **)&scratch, inBytes + outBytes) != hipSuccess)
+         return fail(ctx, NFCGPU_ENOMEM, "spectrum scratch allocation failed");
+
+      hipError_t err = hipMemcpy(scratch, iq, inBytes, hipMemcpyHostToDevice);
+      if (err != hipSuccess)
+      {
+         (void)hipFree(scratch);
+         return fail(ctx, NFCGPU_EHIP, "hipMemcpy(H2D spectrum input)", err);
+      }
+
+      A.iq = (const float2 *)scratch;
+      A.out = (float *)(scratch + inBytes);
+   }
+
+   A.inPitchPairs = inPitch / 8;
+   A.outPitchFloats = outPitch / 4;
+   A.total = (uint64_t)nBuffers * frames;
+   A.frames = frames;
+   A.hop = params->hop;
+   A.decimation = decimation;
+
+   /* one workgroup per frame; beyond 2^20 workgroups each takes several frames */
+   const dim3 grid((uint32_t)(A.total < (1u << 20) ? A.total : (1u << 20)));
+
+   switch (L)
+   {
+      case 256: hipLaunchKernelGGL(nfc_spectrum_kernel_256, grid, dim3(NfcSpectrumShape<256>::kThreads), 0, ctx->stream, A); break;
+      case 512: hipLaunchKernelGGL(nfc_spectrum_kernel_512, grid, dim3(NfcSpectrumShape<512>::kThreads), 0, ctx->stream, A); break;
+      case 1024: hipLaunchKernelGGL(nfc_spectrum_kernel_1024, grid, dim3(NfcSpectrumShape<1024>::kThreads), 0, ctx->stream, A); break;
+      case 2048: hipLaunchKernelGGL(nfc_spectrum_kernel_2048, grid, dim3(NfcSpectrumShape<2048>::kThreads), 0, ctx->stream, A); break;
+      default: hipLaunchKernelGGL(nfc_spectrum_kernel_4096, grid, dim3(NfcSpectrumShape<4096>::kThreads), 0, ctx->stream, A); break;
+   }
+
+   hipError_t err = hipGetLastError();
+   if (err == hipSuccess)
+      err = hipStreamSynchronize(ctx->stream);
+
+   if (err == hipSuccess && location == NFCGPU_LOC_HOST)
+   {
+      /* the frames of every buffer go to the caller's rows; what lies between the rows is the caller's */
+      std::vector<uint8_t> back(outBytes);
+      err = hipMemcpy(back.data(), A.out, outBytes, hipMemcpyDeviceToHost);
+      if (err == hipSuccess)
+      {
+         for (uint32_t b = 0; b < nBuffers; b++)
+            std::memcpy((uint8_t *)out + (size_t)b * outPitch, back.data() + (size_t)b * outPitch, (size_t)rowBytes);
+      }
+   }
+
+   if (scratch)
+      (void)hipFree(scratch);
+
+   if (err != hipSuccess)
+      return fail(ctx, NFCGPU_EHIP, "spectrum", err);
 
    return NFCGPU_OK;
 }

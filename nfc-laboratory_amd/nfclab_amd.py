@@ -93,6 +93,21 @@ class Stats(ctypes.Structure):
     ]
 
 
+class SpectrumParams(ctypes.Structure):
+    _fields_ = [
+        ("length", ctypes.c_uint32),
+        ("window", ctypes.c_uint32),
+        ("decimation", ctypes.c_uint32),
+        ("hop", ctypes.c_uint32),
+        ("sample_rate", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 3),
+    ]
+
+
+# the reference's window names (FourierProcessTask.cpp:121-143; see include/nfcgpu.h for what they compute)
+WINDOWS = {"none": 0, "hamming": 1, "hann": 2}
+
+
 class NfcGpuError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("nfcgpu error %d: %s" % (code, message))
@@ -131,6 +146,11 @@ def load_library(path=LIB_PATH):
     lib.nfcgpu_submit_uniform.argtypes = [vp, u32, u32, vp, u64, u32, u32, u32, u32]
     lib.nfcgpu_magnitude.argtypes = [vp, vp, u64, vp, u32]
     lib.nfcgpu_resample_radio.argtypes = [vp, vp, u64, u32, u32, vp, u64, u32, vp, u32]
+    lib.nfcgpu_spectrum_default_params.argtypes = [P(SpectrumParams)]
+    lib.nfcgpu_spectrum_default_params.restype = None
+    lib.nfcgpu_spectrum_frames.argtypes = [P(SpectrumParams), u32]
+    lib.nfcgpu_spectrum_frames.restype = u32
+    lib.nfcgpu_spectrum.argtypes = [vp, vp, u64, u32, u32, P(SpectrumParams), vp, u64, u32]
     lib.nfcgpu_flush.argtypes = [vp, u32]
     lib.nfcgpu_sync.argtypes = [vp]
     lib.nfcgpu_poll.argtypes = [vp, u32, P(Frame), u32, P(u32)]
@@ -257,6 +277,39 @@ class NfcGpu:
         """Same with device pointers (input, output and counts resident in HBM)."""
         self._check(self.lib.nfcgpu_resample_radio(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, out_ptr, out_pitch_bytes,
                                                    capacity_pairs, counts_ptr, LOC_DEVICE))
+
+    def spectrum_params(self, length=1024, window="hamming", decimation=0, hop=0, sample_rate=10000000):
+        p = SpectrumParams()
+        self.lib.nfcgpu_spectrum_default_params(ctypes.byref(p))
+        p.length, p.decimation, p.hop, p.sample_rate = length, decimation, hop, sample_rate
+        p.window = WINDOWS[window] if isinstance(window, str) else window
+        return p
+
+    def spectrum_frames(self, n_pairs, **params):
+        """Frames a buffer of n_pairs IQ pairs gives with these parameters (nfcgpu_spectrum_frames)."""
+        return self.lib.nfcgpu_spectrum_frames(ctypes.byref(self.spectrum_params(**params)), n_pairs)
+
+    def spectrum(self, buffers, length=1024, window="hamming", decimation=0, hop=0, sample_rate=10000000):
+        """Magnitude spectra of a float32 array [n_buffers, n_pairs, 2] of IQ buffers (host memory), as the reference's
+        FourierProcessTask publishes them (negative frequencies first): [n_buffers, frames, length]; hop = 0 gives the one
+        frame the task publishes for a buffer, hop > 0 a frame every hop pairs."""
+        buffers = np.ascontiguousarray(buffers, dtype=np.float32)
+        nb, n, two = buffers.shape
+        assert two == 2
+        p = self.spectrum_params(length, window, decimation, hop, sample_rate)
+        frames = self.lib.nfcgpu_spectrum_frames(ctypes.byref(p), n)
+        out = np.zeros((nb, frames, length), dtype=np.float32)
+        self._check(self.lib.nfcgpu_spectrum(self.ctx, buffers.ctypes.data, n * 8, nb, n, ctypes.byref(p), out.ctypes.data,
+                                             frames * length * 4, LOC_HOST))
+        return out
+
+    def spectrum_device(self, in_ptr, in_pitch_bytes, n_buffers, n_pairs, out_ptr, out_pitch_bytes, length=1024, window="hamming",
+                        decimation=0, hop=0, sample_rate=10000000):
+        """Same with device pointers (IQ and spectra resident in HBM); returns the frames written per buffer."""
+        p = self.spectrum_params(length, window, decimation, hop, sample_rate)
+        self._check(self.lib.nfcgpu_spectrum(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_pairs, ctypes.byref(p), out_ptr,
+                                             out_pitch_bytes, LOC_DEVICE))
+        return self.lib.nfcgpu_spectrum_frames(ctypes.byref(p), n_pairs)
 
     def flush(self, stream):
         self._check(self.lib.nfcgpu_flush(self.ctx, stream))
