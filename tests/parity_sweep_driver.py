@@ -1,7 +1,7 @@
 """Driver of tests/test_parity_at_size.py. Parity at size, on the GPU: S streams x L samples x K submissions of the sparse /
 dense synthetic set through the C ABI (IQ resident in HBM), EVERY stream compared frame by frame with the reference
 decoder (oracle/_ref, one decoder per stream, a pool of host threads). Prints one JSON object.
-usage: python tests/parity_sweep_driver.py sparse|dense|offgrid S L K   (NFCGPU_* knobs apply; the test sets none)"""
+usage: python tests/parity_sweep_driver.py sparse|dense|offgrid|modulated S L K   (NFCGPU_* knobs apply; the test sets none)"""
 import json, os, sys, time
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,7 +18,24 @@ template = synth.load_template(os.path.join(ROOT, "tests", "golden"))
 template_dev = torch.from_numpy(template.astype(np.int16)).to(dev)
 T = K * L
 data = torch.empty((S, T, 2), dtype=torch.float32, device=dev)
-if kind == "sparse":
+if kind == "modulated":
+    # the modulated exchanges that no capture holds (tests/modulated_cases.py: the scenarios at 10 MS/s but the two long waits, on the
+    # int16 grid): every stream a seeded permutation of them, end to end, cut at a seeded sample of its first scenario
+    import modulated_cases
+    pool = [modulated_cases.build(c, grid=True)[0] for c in modulated_cases.CASES if c.fs == FS and c.where == "all"]
+    for s in range(S):
+        rng = np.random.default_rng(20261016 + FIRST + s)
+        order = rng.permutation(len(pool))
+        shift = int(rng.integers(0, pool[order[0]].size))
+        parts, have = [], -shift
+        for i in order:
+            parts.append(pool[i])
+            have += pool[i].size
+            if have >= T:
+                break
+        data[s, :, 0] = torch.from_numpy(np.concatenate(parts)[shift:shift + T]).to(dev)
+        data[s, :, 1] = 0
+elif kind == "sparse":
     synth.fill_sparse_iq_torch(data, template_dev, synth.sparse_segments(template), first_stream=FIRST, chunk_streams=max(1, min(256, (1 << 26) // T)))
 else:
     synth.fill_iq_torch(data, template_dev, first_stream=FIRST, chunk_streams=max(1, min(1024, (1 << 26) // T)))

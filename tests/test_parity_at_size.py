@@ -71,3 +71,15 @@ def test_off_grid_streams_in_two_submissions_match_the_reference(built):
     stream stays on the time-parallel path (its carry lane decodes it alone, the running sums walked in the reference's order)."""
     res = _check(_sweep("offgrid", 512, 1 << 19, 2))
     assert res["time_parallel_streams"] == 1024 and res["sequential_streams"] == 0, res
+
+
+@needs_reference
+@pytest.mark.gpu
+def test_modulated_exchanges_tiled_to_512_streams_match_the_reference(built):
+    """the scenario table of tests/modulated_cases.py (exchanges that no capture holds: long frames, every defect, protocol feedback,
+    weak signals) at size: 512 streams x 2^20 samples on the int16 grid, each a seeded permutation of the scenarios end to end, cut
+    at a seeded sample, in two submissions, default knobs, EVERY stream compared.
+    Measured on the MI355X: 16 s for this test (building the streams, the submissions, the reference on 512 streams); the dense
+    512-stream test beside it takes 13 s, the sparse config-5 test 85 s."""
+    res = _check(_sweep("modulated", 512, 1 << 19, 2))
+    assert res["time_parallel_streams"] + res["sequential_streams"] == 1024, res

@@ -10,6 +10,7 @@ import sys
 
 import pytest
 
+import modulated_cases as MC
 import nfc_testlib as T
 
 DRIVER = os.path.join(T.ROOT, "tests", "time_parallel_driver.py")
@@ -218,6 +219,68 @@ def test_random_multi_submission_scenarios_on_the_gpu(built):
     assert run.returncode == 0, run.stderr[-2000:]
     res = json.loads(run.stdout.strip().splitlines()[-1])
     assert res["rounds"] >= 5 and res["mismatches"] == [], res
+
+
+# ---- modulated exchanges that no capture holds (tests/modulated_cases.py). The emulated runtime decodes some 100 000 samples a second
+# on the grid and 20 000 off it, so on the CPU: the scenarios of groups 1-3 at 10 MS/s that are shorter than 2^19 samples on the
+# grid, five of them off the grid, six where chunks of 8192 samples put seams into long frames and waiting windows. On the device:
+# everything at 10 MS/s.
+MOD_LONG = {"a106 short and long", "b106 short and long", "v 1-of-4 short and long", "a106 answers absent, early and late", "b106 truncated",
+            "f212 truncated", "v answers absent, early and late", "a106 rats fsdi 8 then frames over 256 bytes", "b106 atqb fsdi 8 fwi 7",
+            "b106 attrib tr0 1 fsdi 8"}                                       # 2^19 samples and more
+MOD_HOST = [c.name for c in MC.CASES if c.group <= 3 and c.where == "all" and c.fs == MC.FS and c.name not in MOD_LONG]
+MOD_HOST_OFFGRID = ["a424 short and long", "b106 wrong crc", "f424 wrong crc and sync", "v wrong crc", "a106 ats fwi 4"]
+MOD_HOST_SEAMS = ["a212 short and long", "a106 ats fwi 0", "a106 ats fwi 4", "a106 rats fsdi 5 then frames over 64 bytes", "b106 atqb fsdi 5 fwi 4",
+                  "f212 reqc with 4 slots"]
+# (the path takes streams of the default configuration at 10 MS/s alone - matches_fixed_table, nfcgpu.hip; the scenarios at 5 and
+# 2.5 MS/s go to the sequential kernels: tests/test_modulated_gpu.py has them)
+MOD_EVERYTHING = [c.name for c in MC.CASES if c.fs == MC.FS]
+MOD_SEAMS = [c.name for c in MC.CASES if c.group in (1, 3) and c.fs == MC.FS]  # the long frames and the protocol feedback, the long waits with them
+
+
+def _modulated(names, kind, buffers):
+    return "modulated:%s:%d:%s" % (kind, buffers, ",".join(str(MC.CASES.index(MC.BY_NAME[n])) for n in names))
+
+
+def _check_modulated(res, streams):
+    _check(res)
+    assert sum(int(r["name"].split()[0]) for r in res) == streams and sum(r["frames"] for r in res) > 3 * streams, res   # (more than the three carrier frames that open every stream)
+
+
+@needs_reference
+@pytest.mark.parametrize("buffers", [1, 3])
+def test_modulated_exchanges_on_the_grid_emulated(emulated, buffers):
+    """speculative windows and the wave decoder's bulk paths over frames up to 250 bytes, every defect and the protocol feedback"""
+    _check_modulated(_run([_modulated(MOD_HOST, "grid", buffers)], True), len(MOD_HOST))
+
+
+@needs_reference
+def test_modulated_exchanges_off_the_grid_emulated(emulated):
+    """as the modulator gives them: carry lanes alone, walked sums"""
+    _check_modulated(_run([_modulated(MOD_HOST_OFFGRID, "offgrid", 1)], True), len(MOD_HOST_OFFGRID))
+
+
+@needs_reference
+def test_modulated_exchanges_with_seams_inside_frames_and_waiting_windows_emulated(emulated):
+    """chunks of 8192 samples with 1024 of warm-up: a piece starts inside a frame of 250 bytes, or inside a waiting window whose
+    length an earlier frame has set (RATS / ATS, ATQB, REQC with time slots)"""
+    res = _run([_modulated(MOD_HOST_SEAMS, "grid", 1)], True, {"NFCGPU_SCAN_CHUNK": "8192", "NFCGPU_SCAN_WARM": "1024"})
+    _check_modulated(res, len(MOD_HOST_SEAMS))
+    assert sum(r["stats"]["repairs"] for r in res) > 0
+
+
+@needs_reference
+@pytest.mark.gpu
+def test_modulated_exchanges_on_the_gpu(built):
+    """every scenario at 10 MS/s, the long waits of FWI 8 and 14 with them: on the grid in 1 and in 3 buffers, off the grid, and on the grid
+    with small chunks"""
+    for buffers in (1, 3):
+        _check_modulated(_run([_modulated(MOD_EVERYTHING, "grid", buffers)], False), len(MOD_EVERYTHING))
+    res = _run([_modulated(MOD_EVERYTHING, "offgrid", 1)], False)
+    _check_modulated(res, len(MOD_EVERYTHING))
+    res = _run([_modulated(MOD_SEAMS, "grid", 1)], False, {"NFCGPU_SCAN_CHUNK": "8192", "NFCGPU_SCAN_WARM": "1024"})
+    _check_modulated(res, len(MOD_SEAMS))
+    assert sum(r["stats"]["repairs"] for r in res) > 0
 
 
 @needs_reference

@@ -18,7 +18,7 @@ import synth
 FS = 10000000
 
 
-def decode(streams, buffers=1, stride=1):
+def decode(streams, buffers=1, stride=1, fs=FS):
     """streams: list of float32 magnitude arrays; returns (frames per stream, stats)"""
     with nfclab_amd.NfcGpu(device=0, max_streams=max(64, len(streams))) as gpu:
         first = gpu.open(count=len(streams))
@@ -34,16 +34,16 @@ def decode(streams, buffers=1, stride=1):
             ids = [first + i for i, p in enumerate(parts) if p.size]
             ptrs = [p.ctypes.data for p in parts if p.size]
             cnts = [p.size // stride for p in parts if p.size]
-            gpu.submit_batch(ids, ptrs, cnts, FS, stride=stride)
+            gpu.submit_batch(ids, ptrs, cnts, fs, stride=stride)
         got = [gpu.poll(first + i, capacity=16384) for i in range(len(streams))]
         st = gpu.stats()
     return got, {"windowed": int(st.windowed_streams), "fallback": int(st.fallback_streams), "windows": int(st.windows),
                  "passes": int(st.window_passes), "repairs": int(st.scan_repairs)}
 
 
-def case(name, streams, **kw):
-    want = [T.reference_decode(m, keep_carrier=True, cap=16384, defined_storage=True)[0] for m in streams]
-    got, st = decode(streams, **kw)
+def case(name, streams, fs=FS, **kw):
+    want = [T.reference_decode(m, sample_rate=fs, keep_carrier=True, cap=16384, defined_storage=True)[0] for m in streams]
+    got, st = decode(streams, fs=fs, **kw)
     bad = [i for i in range(len(streams)) if got[i] != want[i]]
     return {"name": name, "frames": sum(len(w) for w in want), "mismatching": bad, "stats": st}
 
@@ -62,6 +62,16 @@ def main():
         if head is not None:
             mag = np.ascontiguousarray(mag[:int(head)])
         out.append(case(name if head is None else "%s@%s" % (name, head), [mag]))
+
+    # "modulated:grid|offgrid:<buffers>:<i>,<j>,...": scenarios of tests/modulated_cases.py by their place in its table (modulated
+    # exchanges that no capture holds), rounded onto the int16 grid or as they are, the streams of one sample rate in one case
+    for word in [w for w in which if w.startswith("modulated:")]:
+        import modulated_cases
+        _, kind, buffers, places = word.split(":")
+        chosen = [modulated_cases.CASES[int(i)] for i in places.split(",")]
+        for fs in sorted({c.fs for c in chosen}, reverse=True):
+            streams = [modulated_cases.build(c, grid=(kind == "grid"))[0] for c in chosen if c.fs == fs]
+            out.append(case("%d modulated scenarios at %g MS/s, %s, %s buffers" % (len(streams), fs / 1e6, kind, buffers), streams, fs=fs, buffers=int(buffers)))
 
     if not which or "fixtures" in which:
         for name in T.fixture_names():
