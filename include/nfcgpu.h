@@ -20,6 +20,11 @@
  *                                      RadioDeviceTask::processQueue (lab-tasks/.../RadioDeviceTask.cpp:547-656) fused in
  *   nfcgpu_submit_batch / _uniform     the same call for many independent streams at once (the reference would run one
  *                                      NfcDecoder per stream on one thread each); inputs may already be resident in HBM
+ *   nfcgpu_submit_fmt / _batch_fmt /   the same calls for samples in the format capture files hold them in: 16-bit PCM, as
+ *   _uniform_fmt, nfcgpu_magnitude_fmt SignalStorageTask::writeRadio records and readRadio replays. The kernels convert while they
+ *                                      load, value = (float)v / 32768.0f: the widening hw::RecordDevice::readScaledSamples<short>
+ *                                      does on the host (lib-hw/hw-radio .../RecordDevice.cpp:247-248, 281-311) and the fp32 copy
+ *                                      of the capture it makes are skipped
  *   nfcgpu_flush                       NfcDecoder::nextFrames(invalid buffer) -> one carrier-state frame (NfcDecoder.cpp:449-463)
  *   nfcgpu_poll                        the returned std::list<lab::RawFrame> (lab-data/src/main/cpp/RawFrame.cpp:26-98)
  *   nfcgpu_stream_close                ~NfcDecoder
@@ -56,6 +61,10 @@ extern "C" {
 
 #define NFCGPU_LOC_HOST 0u
 #define NFCGPU_LOC_DEVICE 1u
+
+/* sample formats of the decoder's input (the _fmt entry points; one format per call, as one stride per call) */
+#define NFCGPU_FMT_F32 0u /* float, what every entry point without _fmt takes */
+#define NFCGPU_FMT_I16 1u /* little-endian int16 PCM, value = (float)v / 32768.0f (RecordDevice.cpp:247-248, 297-300) */
 
 typedef struct nfcgpu_ctx nfcgpu_ctx;
 
@@ -96,7 +105,8 @@ typedef struct nfcgpu_options
    uint64_t frame_sink_bytes; /* device frame sink per sync interval; default 64 MiB */
 } nfcgpu_options;
 
-/* many streams, one call. data[i] points to n_samples[i]*stride floats of stream stream_ids[i] */
+/* many streams, one call. data[i] points to n_samples[i]*stride floats of stream stream_ids[i] (nfcgpu_submit_batch_fmt: values
+ * of the call's format) */
 typedef struct nfcgpu_batch
 {
    uint32_t n_streams;
@@ -172,6 +182,22 @@ int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *batch);
 int nfcgpu_submit_uniform(nfcgpu_ctx *ctx, uint32_t first_stream_id, uint32_t count, const void *base, uint64_t pitch_bytes,
                           uint32_t n_samples, uint32_t stride, uint32_t location, uint32_t sample_rate);
 
+/* The same calls with a sample format (NFCGPU_FMT_*). `stride` keeps its meaning (1 magnitude, 2 interleaved IQ); a sample is
+ * stride * 4 bytes of NFCGPU_FMT_F32 or stride * 2 bytes of NFCGPU_FMT_I16, and data pointers, base and pitch_bytes must be
+ * multiples of that (2 bytes for int16 magnitude, 4 for int16 IQ; NFCGPU_EINVAL otherwise, as for an unknown format). With
+ * NFCGPU_FMT_F32 they are the calls above, to the error codes and texts. The kernels read int16 where it lies - host input
+ * is staged as int16, n * stride * 2 bytes per row, device input is read in place - and convert on load; no fp32 copy of a
+ * submission is made. The conversion is exact (a power-of-two scale of a 16-bit integer; IQ components are converted and
+ * then go through the same magnitude formula), so any sequence of calls with int16 buffers gives exactly the frames, in
+ * every field and in the same order, that it gives with float buffers holding (float)v / 32768.0f - and takes the
+ * time-parallel path exactly when those would. A stream may receive floats in one call and int16 in the next: stream
+ * state does not know the format. */
+int nfcgpu_submit_fmt(nfcgpu_ctx *ctx, uint32_t stream_id, const void *data, uint32_t n_samples, uint32_t stride, uint32_t sample_rate,
+                      uint32_t format);
+int nfcgpu_submit_batch_fmt(nfcgpu_ctx *ctx, const nfcgpu_batch *batch, uint32_t format);
+int nfcgpu_submit_uniform_fmt(nfcgpu_ctx *ctx, uint32_t first_stream_id, uint32_t count, const void *base, uint64_t pitch_bytes,
+                              uint32_t n_samples, uint32_t stride, uint32_t location, uint32_t sample_rate, uint32_t format);
+
 /* Magnitude of interleaved float IQ, out[i] = sqrtf(I*I + Q*Q) with the reference's roundings (products and sum
  * rounded separately, correctly rounded root): the conversion RadioDeviceTask applies before publishing a
  * SIGNAL_TYPE_RADIO_SAMPLES buffer (RadioDeviceTask.cpp:547-656, scalar form 626-642). The decoder entry points do
@@ -179,6 +205,8 @@ int nfcgpu_submit_uniform(nfcgpu_ctx *ctx, uint32_t first_stream_id, uint32_t co
  * magnitudes (storage, display) and for bit-exact testing. `location` applies to both pointers; the call returns
  * when `out` is complete. */
 int nfcgpu_magnitude(nfcgpu_ctx *ctx, const float *iq, uint64_t n_samples, float *out, uint32_t location);
+/* the same for IQ in `format`: int16 components (4-byte aligned pairs) are converted, (float)v / 32768.0f, then the same formula */
+int nfcgpu_magnitude_fmt(nfcgpu_ctx *ctx, const void *iq, uint64_t n_samples, float *out, uint32_t location, uint32_t format);
 
 /* Adaptive resampling of magnitude buffers for display, the radio branch of the reference's SignalResamplingTask
  * (SignalResamplingTask.cpp:168-226: `processRadioSignal`, the other per-sample consumer of "radio.signal.raw"): every

@@ -20,19 +20,17 @@
 #include "nfc_launch.h"
 #include "nfc_scan_launch.h"
 
-/* magnitude of one IQ sample, the reference's scalar formula (RadioDeviceTask.cpp:626-642): products and sum rounded
- * separately (no contraction), correctly rounded square root - as nfc_kernels.hip forms it */
-__device__ __forceinline__ float nfc_envelope_sample_at(const uint8_t *data, uint32_t stride, uint32_t index)
-{
-   if (stride == 2)
-   {
-      const float2 iq = reinterpret_cast<const float2 *>(data)[index];
-      return __builtin_sqrtf(__fadd_rn(__fmul_rn(iq.x, iq.x), __fmul_rn(iq.y, iq.y)));
-   }
-   return reinterpret_cast<const float *>(data)[index];
-}
+/* a sample (magnitude / IQ) as a magnitude, as nfc_kernels.hip forms it. This text is compiled twice: as it is for float input,
+ * and with -DNFC_INPUT_I16 for int16 PCM (nfc_envelope_kernel_i16) */
+#include "nfc_sample.hpp"
 
-#define NFC_SAMPLE_AT(data, stride, index) nfc_envelope_sample_at((data), (stride), (index))
+#ifdef NFC_INPUT_I16
+#define NFC_SAMPLE_AT(data, stride, index) nfc_sample_at_as<true>((data), (stride), (index))
+#define NFC_ENVELOPE_KERNEL_NAME nfc_envelope_kernel_i16
+#else
+#define NFC_SAMPLE_AT(data, stride, index) nfc_sample_at_as<false>((data), (stride), (index))
+#define NFC_ENVELOPE_KERNEL_NAME nfc_envelope_kernel
+#endif
 
 /* sample-rate-derived constants of the most common configuration as literals (generated at build time) */
 #define NFC_FIXED_FN __device__ __forceinline__
@@ -88,7 +86,7 @@ __device__ __forceinline__ void nfc_envelope_verify(const NfcConfig &c, float en
 #include "nfc_envelope.hpp"
 
 /* one wavefront per listed chunk (nfc_envelope_rewalk_wave) */
-__global__ __launch_bounds__(64) void nfc_envelope_kernel(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A)
+__global__ __launch_bounds__(64) void NFC_ENVELOPE_KERNEL_NAME(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A)
 {
    const uint32_t listed = blockIdx.x;
 

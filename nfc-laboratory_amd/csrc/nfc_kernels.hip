@@ -22,24 +22,10 @@
 
 #include "nfc_core.hpp"
 
-/* magnitude of one IQ sample, the reference's scalar formula (RadioDeviceTask.cpp:626-642): products and sum rounded
- * separately (no contraction), correctly rounded square root */
-__device__ __forceinline__ float nfc_iq_magnitude(float i, float q)
-{
-   return __builtin_sqrtf(__fadd_rn(__fmul_rn(i, i), __fmul_rn(q, q)));
-}
+/* nfc_iq_magnitude, nfc_sample_at, the sample layouts (float / int16, magnitude / IQ) */
+#include "nfc_sample.hpp"
 
-__device__ __forceinline__ float nfc_sample_at(const uint8_t *data, uint32_t stride, uint32_t index)
-{
-   if (stride == 2)
-   {
-      const float2 iq = reinterpret_cast<const float2 *>(data)[index];
-      return nfc_iq_magnitude(iq.x, iq.y);
-   }
-   return reinterpret_cast<const float *>(data)[index];
-}
-
-#define NFC_SAMPLE_AT(data, stride, index) nfc_sample_at((data), (stride), (index))
+#define NFC_SAMPLE_AT(data, stride, index) nfc_sample_at_as<false>((data), (stride), (index))
 #define NFC_FENCE() __threadfence()
 /* a window record written by the 64 lanes of the wave that builds a stream's windows (nfc_windows_kernel; every lane is there with
  * the same values): lane d + 64 k writes word d + 64 k - the record's first four words are the ones that are not zero */
@@ -125,10 +111,12 @@ __device__ __forceinline__ NfcRow nfc_row(const NfcLaunch &L, uint32_t slot)
 /* Stage samples [base, base + TILE) of the 64 streams of a block into LDS as magnitudes, transposed: row r of the
  * tile is stream r, and one wave-wide load fetches 64 consecutive samples of one stream (512 B of IQ, 256 B of
  * magnitude). Rows are fetched NFC_STAGE_ROWS at a time, all loads of a batch in flight together; samples past the
- * end of a row read as zero (their lanes never consume them). S = floats per sample (2 IQ, 1 magnitude). */
+ * end of a row read as zero (their lanes never consume them). S = components per sample (2 IQ, 1 magnitude); I16: the components are
+ * int16 PCM (nfc_sample.hpp), a row 128 B of magnitude or 256 B of IQ. Mono int16 rows are 2-byte aligned only (a slice starts at any
+ * sample): they are loaded as 16-bit values. */
 #define NFC_STAGE_ROWS 16
 
-template <uint32_t S>
+template <uint32_t S, bool I16 = false>
 __device__ __forceinline__ void nfc_stage_tile(const NfcLaunch &L, uint32_t block, uint32_t base, uint32_t lane, float *tile)
 {
    const uint32_t idx = base + lane;
@@ -151,7 +139,18 @@ __device__ __forceinline__ void nfc_stage_tile(const NfcLaunch &L, uint32_t bloc
 
          count[j] = row.count;
 
-         if (S == 2)
+         if (I16 && S == 2)
+         {
+            const NfcIq16 iq = reinterpret_cast<const NfcIq16 *>(p)[at];
+            re[j] = nfc_i16_to_float(iq.i);
+            im[j] = nfc_i16_to_float(iq.q);
+         }
+         else if (I16)
+         {
+            re[j] = nfc_i16_to_float(reinterpret_cast<const int16_t *>(p)[at]);
+            im[j] = 0.0f;
+         }
+         else if (S == 2)
          {
             const float2 iq = reinterpret_cast<const float2 *>(p)[at];
             re[j] = iq.x;
@@ -174,7 +173,9 @@ __device__ __forceinline__ void nfc_stage_tile(const NfcLaunch &L, uint32_t bloc
    }
 }
 
-template <bool EXACT, bool FIXED>
+/* I16: the launch's rows are int16 PCM (a kernel of its own per format: the float kernels are compiled as they were before there was
+ * a second format, to the instruction) */
+template <bool EXACT, bool FIXED, bool I16>
 __device__ __forceinline__ void nfc_demod_body(const NfcConfig *__restrict__ cfgPtr, const NfcLaunch &L, float *tile)
 {
    const uint32_t lane = threadIdx.x;
@@ -230,10 +231,10 @@ __device__ __forceinline__ void nfc_demod_body(const NfcConfig *__restrict__ cfg
 
    for (uint32_t base = 0; base < longest; base += TILE)
    {
-      if (L.uniformStride == 2)
-         nfc_stage_tile<2>(L, block, base, lane, tile);
+      if (L.uniformStride == (I16 ? (NFC_SAMPLE_I16 | 2u) : 2u))
+         nfc_stage_tile<2, I16>(L, block, base, lane, tile);
       else
-         nfc_stage_tile<1>(L, block, base, lane, tile);
+         nfc_stage_tile<1, I16>(L, block, base, lane, tile);
 
       __syncthreads();
 
@@ -292,7 +293,13 @@ __device__ __forceinline__ void nfc_demod_body(const NfcConfig *__restrict__ cfg
    __global__ __launch_bounds__(64) attrs void name(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L) \
    {                                                                                                   \
       __shared__ float tile[NFC_LANES * TILE_PITCH];                                                   \
-      nfc_demod_body<exact, fixed>(cfgPtr, L, tile);                                                   \
+      nfc_demod_body<exact, fixed, false>(cfgPtr, L, tile);                                            \
+   }                                                                                                   \
+   /* the same for launches of int16 rows (NfcLaunch::uniformStride with NFC_SAMPLE_I16) */            \
+   __global__ __launch_bounds__(64) attrs void name##_i16(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L) \
+   {                                                                                                   \
+      __shared__ float tile[NFC_LANES * TILE_PITCH];                                                   \
+      nfc_demod_body<exact, fixed, true>(cfgPtr, L, tile);                                             \
    }
 
 /* exactly NFC_MIN_WAVES waves per SIMD: spilling state to scratch to reach a higher occupancy costs 5-10x */
@@ -315,6 +322,18 @@ __global__ __launch_bounds__(256) void nfc_magnitude_kernel(const float2 *__rest
    {
       const float2 v = iq[i];
       out[i] = nfc_iq_magnitude(v.x, v.y);
+   }
+}
+
+/* the same for int16 IQ: both components converted (nfc_i16_to_float), then the same formula */
+__global__ __launch_bounds__(256) void nfc_magnitude_kernel_i16(const NfcIq16 *__restrict__ iq, float *__restrict__ out, uint64_t n)
+{
+   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+
+   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+   {
+      const NfcIq16 v = iq[i];
+      out[i] = nfc_iq_magnitude(nfc_i16_to_float(v.i), nfc_i16_to_float(v.q));
    }
 }
 
@@ -502,8 +521,8 @@ __device__ __forceinline__ void nfc_fixed_runtime_config(const NfcConfig *cfgPtr
 #define NFC_SCAN_ROWS 16
 #define NFC_SCAN_PITCH (NFC_SCAN_TILE + 1)
 
-/* S = floats per sample (2 IQ, 1 magnitude) */
-template <uint32_t S>
+/* S = components per sample (2 IQ, 1 magnitude); I16: int16 PCM components instead of floats (nfc_sample.hpp) */
+template <uint32_t S, bool I16 = false>
 __device__ __forceinline__ void nfc_scan_body(const NfcConfig *__restrict__ cfgPtr, const NfcScanArgs &A, float *tile, uint32_t *rows)
 {
    const uint32_t lane = threadIdx.x;
@@ -535,7 +554,7 @@ __device__ __forceinline__ void nfc_scan_body(const NfcConfig *__restrict__ cfgP
 
    /* row descriptor (this lane's; the other lanes read it with v_readlane): where the row is at step 0, and the steps'
     * sample range the walk covers: [fromRel, endRel) */
-   const uint64_t rowBase = (uint64_t)(mine ? job->data : (const uint8_t *)A.tileStats) + (int64_t)origin * (int64_t)(S * 4u);
+   const uint64_t rowBase = (uint64_t)(mine ? job->data : (const uint8_t *)A.tileStats) + (int64_t)origin * (int64_t)(S * (I16 ? 2u : 4u));
    const uint32_t rowLo = (uint32_t)rowBase, rowHi = (uint32_t)(rowBase >> 32);
    const uint32_t rowFrom = walkFrom - (uint32_t)origin; /* origin <= walkFrom */
    uint32_t rowEnd = mine ? end - (uint32_t)origin : 0u;  /* (a second walk that meets the first one's trajectory ends early) */
@@ -591,7 +610,16 @@ __device__ __forceinline__ void nfc_scan_body(const NfcConfig *__restrict__ cfgP
          at = at < fromRel ? fromRel : at;
          at = at >= endRel ? endRel - 1u : at;
 
-         if (S == 2)
+         if (I16)
+         {
+            /* 16-bit loads: a mono row may start at any sample, so at any even address */
+            typedef __attribute__((address_space(1))) const int16_t GlobalShort;
+            GlobalShort *p = has ? (GlobalShort *)row + S * at : (GlobalShort *)A.tileStats;
+            const int16_t vx = p[0], vy = S == 2 ? p[1] : (int16_t)0;
+            re[q] = has ? nfc_i16_to_float(vx) : 0.0f;
+            im[q] = has ? nfc_i16_to_float(vy) : 0.0f;
+         }
+         else if (S == 2)
          {
             GlobalFloat *p = has ? (GlobalFloat *)row + 2u * at : (GlobalFloat *)A.tileStats;
             const float vx = p[0], vy = p[1];
@@ -813,6 +841,18 @@ __global__ __launch_bounds__(64) void nfc_scan_kernel(const NfcConfig *__restric
       nfc_scan_body<1>(cfgPtr, A, tile, rows);
 }
 
+/* the same for submissions of int16 samples (NfcScanArgs::stride with NFC_SAMPLE_I16) */
+__global__ __launch_bounds__(64) void nfc_scan_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A)
+{
+   __shared__ float tile[NFC_LANES * NFC_SCAN_PITCH];
+   __shared__ uint32_t rows[NFC_LANES * 4];
+
+   if (A.stride == (NFC_SAMPLE_I16 | 2u))
+      nfc_scan_body<2, true>(cfgPtr, A, tile, rows);
+   else
+      nfc_scan_body<1, true>(cfgPtr, A, tile, rows);
+}
+
 /* The front-end planes (NfcScanArgs::planes: {filtered, envelope, deviation, average} after every sample, 16 B) for the wave
  * decoder: a walk of the front end alone over every chunk from its verified start state, a lane per chunk, the rows fetched
  * and transposed like the scan's.
@@ -826,7 +866,7 @@ __global__ __launch_bounds__(64) void nfc_scan_kernel(const NfcConfig *__restric
 #define NFC_PLANES_GROUP 4u
 #endif
 
-template <uint32_t S>
+template <uint32_t S, bool I16 = false>
 __device__ __forceinline__ void nfc_planes_body(const NfcConfig *__restrict__ cfgPtr, const NfcScanArgs &A, float *tile, float4 *stage, uint64_t *rowOut, uint32_t *rowN)
 {
    const uint32_t lane = threadIdx.x;
@@ -853,7 +893,7 @@ __device__ __forceinline__ void nfc_planes_body(const NfcConfig *__restrict__ cf
    const uint32_t mySamples = end > start ? end - start : 0u;
 
    /* row descriptor (this lane's; the other lanes read it with v_readlane): the chunk's first sample and its length */
-   const uint64_t rowBase = (uint64_t)(mySamples ? job->data : (const uint8_t *)A.tileStats) + (uint64_t)start * (uint64_t)(S * 4u);
+   const uint64_t rowBase = (uint64_t)(mySamples ? job->data : (const uint8_t *)A.tileStats) + (uint64_t)start * (uint64_t)(S * (I16 ? 2u : 4u));
    const uint32_t rowLo = (uint32_t)rowBase, rowHi = (uint32_t)(rowBase >> 32);
 
    NfcConfig cc;
@@ -889,7 +929,16 @@ __device__ __forceinline__ void nfc_planes_body(const NfcConfig *__restrict__ cf
          uint32_t at = rel + lane;
          at = (has && at >= endRel) ? endRel - 1u : at;
 
-         if (S == 2)
+         if (I16)
+         {
+            /* 16-bit loads: a mono row may start at any sample, so at any even address */
+            typedef __attribute__((address_space(1))) const int16_t GlobalShort;
+            GlobalShort *p = has ? (GlobalShort *)row + S * at : (GlobalShort *)A.tileStats;
+            const int16_t vx = p[0], vy = S == 2 ? p[1] : (int16_t)0;
+            re[q] = has ? nfc_i16_to_float(vx) : 0.0f;
+            im[q] = has ? nfc_i16_to_float(vy) : 0.0f;
+         }
+         else if (S == 2)
          {
             GlobalFloat *p = has ? (GlobalFloat *)row + 2u * at : (GlobalFloat *)A.tileStats;
             const float vx = p[0], vy = p[1];
@@ -973,6 +1022,20 @@ __global__ __launch_bounds__(64) void nfc_scan_planes_kernel(const NfcConfig *__
       nfc_planes_body<2>(cfgPtr, A, tile, stage, rowOut, rowN);
    else
       nfc_planes_body<1>(cfgPtr, A, tile, stage, rowOut, rowN);
+}
+
+/* the same for submissions of int16 samples */
+__global__ __launch_bounds__(64) void nfc_scan_planes_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A)
+{
+   __shared__ float tile[NFC_LANES * NFC_SCAN_PITCH];
+   __shared__ float4 stage[NFC_LANES * NFC_PLANES_GROUP];
+   __shared__ uint64_t rowOut[NFC_LANES];
+   __shared__ uint32_t rowN[NFC_LANES];
+
+   if (A.stride == (NFC_SAMPLE_I16 | 2u))
+      nfc_planes_body<2, true>(cfgPtr, A, tile, stage, rowOut, rowN);
+   else
+      nfc_planes_body<1, true>(cfgPtr, A, tile, stage, rowOut, rowN);
 }
 
 /* The chunks whose start state changed after the walk that writes the planes was started (NfcScanArgs::planesStale): listed for
@@ -1272,7 +1335,7 @@ __global__ __launch_bounds__(64) void nfc_window_lanes_kernel(const NfcConfig *_
    }
 
    NfcWork work;
-   work.data = job->data + (uint64_t)w.start * A.stride * 4u;
+   work.data = job->data + (uint64_t)w.start * nfc_sample_bytes(A.stride);
    work.count = 0;
    work.stride = A.stride;
    work.tiles = A.tiles + job->firstTile + w.start / NFC_SCAN_TILE;
@@ -1362,7 +1425,7 @@ __global__ __launch_bounds__(64) void nfc_final_lanes_kernel(const NfcConfig *__
       lanes.cold[to] = cold;
       A.windows[to] = w;
 
-      work.data = job->data + (uint64_t)w.start * A.stride * 4u;
+      work.data = job->data + (uint64_t)w.start * nfc_sample_bytes(A.stride);
       work.count = job->count - w.start;
       work.tiles = A.tiles + job->firstTile + w.start / NFC_SCAN_TILE;
    }

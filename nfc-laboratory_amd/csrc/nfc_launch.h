@@ -11,9 +11,10 @@
 /* input of one stream slot for one launch */
 struct NfcWork
 {
-   const uint8_t *data; /* device pointer: count*stride floats */
+   const uint8_t *data; /* device pointer: count samples of the launch's layout */
    uint32_t count;      /* samples */
-   uint32_t stride;     /* 1 magnitude, 2 interleaved IQ (host bookkeeping; a launch has one format, NfcLaunch::uniformStride) */
+   uint32_t stride;     /* sample layout (nfc_sample.hpp): 1 magnitude, 2 interleaved IQ for floats, | NFC_SAMPLE_I16 for int16
+                           (host bookkeeping; a launch has one layout, NfcLaunch::uniformStride) */
    const uint32_t *tiles; /* windowed launches: tile flag words (nfc_scan.h) from the lane's first sample on */
 };
 
@@ -29,7 +30,8 @@ struct NfcLaunch
    const uint8_t *uniformBase;
    uint64_t uniformPitch;
    uint32_t uniformCount;
-   uint32_t uniformStride; /* floats per sample of every row of the launch (both layouts): 1 magnitude, 2 IQ */
+   uint32_t uniformStride; /* sample layout of every row of the launch, table or uniform (nfc_sample.hpp): floats per sample for float
+                              input - 1 magnitude, 2 IQ -, the same | NFC_SAMPLE_I16 (0x101, 0x102) for int16 */
    uint32_t sinkWords;
    uint32_t firstBlock;
    uint32_t firstSlot;

@@ -88,7 +88,7 @@ struct NfcScanSeam
 /* one stream of a submission */
 struct NfcScanJob
 {
-   const uint8_t *data; /* device pointer, count*stride floats */
+   const uint8_t *data; /* device pointer, count samples of the submission's layout (NfcScanArgs::stride) */
    uint32_t count;      /* samples */
    uint32_t slot;       /* stream slot holding the state the submission starts from */
    uint32_t firstChunk; /* index of its first chunk in the chunk table */

@@ -30,7 +30,8 @@ struct NfcScanArgs
    uint32_t nChunks;
    const NfcScanChunk *chunksMore; /* the scan kernel's list goes on here (a round's two repair lists in one launch) */
    uint32_t nChunksMore;
-   uint32_t stride;            /* floats per sample of every job: 1 magnitude, 2 IQ */
+   uint32_t stride;            /* sample layout of every job (nfc_sample.hpp): floats per sample for float input - 1 magnitude, 2 IQ -,
+                                  the same | NFC_SAMPLE_I16 for int16 */
    NfcScanParams params;
    const NfcStreamState *states; /* the streams' own slots (state a submission starts from) */
    NfcScanPoint *points;

@@ -48,22 +48,16 @@ __device__ __forceinline__ uint32_t nfc_wave_x_old_index(const NFC_RING_FLOAT *r
 
 #include "nfc_core.hpp"
 
-__device__ __forceinline__ float nfc_iq_magnitude(float i, float q)
-{
-   return __builtin_sqrtf(__fadd_rn(__fmul_rn(i, i), __fmul_rn(q, q)));
-}
+/* a sample (magnitude / IQ) as a magnitude. This text is compiled twice: as it is for float input, and with -DNFC_INPUT_I16 for
+ * int16 PCM (nfc_wave_kernel_i16) */
+#include "nfc_sample.hpp"
 
-__device__ __forceinline__ float nfc_sample_at(const uint8_t *data, uint32_t stride, uint32_t index)
-{
-   if (stride == 2)
-   {
-      const float2 iq = reinterpret_cast<const float2 *>(data)[index];
-      return nfc_iq_magnitude(iq.x, iq.y);
-   }
-   return reinterpret_cast<const float *>(data)[index];
-}
-
-#define NFC_SAMPLE_AT(data, stride, index) nfc_sample_at((data), (stride), (index))
+#ifdef NFC_INPUT_I16
+#define NFC_SAMPLE_AT(data, stride, index) nfc_sample_at_as<true>((data), (stride), (index))
+#define NFC_WAVE_KERNEL_NAME nfc_wave_kernel_i16
+#else
+#define NFC_SAMPLE_AT(data, stride, index) nfc_sample_at_as<false>((data), (stride), (index))
+#endif
 #define NFC_FENCE() __threadfence()
 #include "nfc_scan.hpp"
 

@@ -26,6 +26,7 @@
 #include "nfc_launch.h"
 #include "nfc_scan_launch.h"
 #include "nfc_spectrum.hpp"
+#include "nfc_sample.hpp"
 
 __global__ void nfc_demod_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
 __global__ void nfc_demod_exact_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
@@ -54,6 +55,24 @@ __global__ void nfc_scan_planes_kernel(const NfcConfig *__restrict__ cfgPtr, Nfc
 __global__ void nfc_envelope_kernel(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A);
 __global__ void nfc_wave_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L, NfcScanArgs A, uint32_t mode);
 __global__ void nfc_planes_stale_kernel(NfcScanArgs A, const NfcScanChunk *all, uint32_t nAll, NfcScanChunk *out, uint32_t *count);
+
+/* The kernels that read samples exist once per sample format (nfc_sample.hpp): the int16 ones are the same text compiled for
+ * int16 rows, so that the float ones stay the code they were. NFC_BY_LAYOUT picks by a submission's layout. (The emulated test
+ * build has twins of the float kernels only and widens int16 input before it gets here: widen_i16.) */
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+#define NFC_BY_LAYOUT(layout, kernel) (kernel)
+#else
+__global__ void nfc_demod_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
+__global__ void nfc_demod_exact_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
+__global__ void nfc_demod_fixed_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
+__global__ void nfc_demod_fixed_exact_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
+__global__ void nfc_magnitude_kernel_i16(const NfcIq16 *__restrict__ iq, float *__restrict__ out, uint64_t n);
+__global__ void nfc_scan_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A);
+__global__ void nfc_scan_planes_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A);
+__global__ void nfc_envelope_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcScanArgs A);
+__global__ void nfc_wave_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L, NfcScanArgs A, uint32_t mode);
+#define NFC_BY_LAYOUT(layout, kernel) (((layout) & NFC_SAMPLE_I16) ? kernel##_i16 : kernel)
+#endif
 
 #ifdef NFCGPU_EMULATED_TEST_BUILD
 /* The test build's twins of the spectrum kernels (nfc_spectrum.hip): the same steps from nfc_spectrum.hpp, the grid, the
@@ -177,6 +196,9 @@ struct nfcgpu_ctx
    StageSlot stage[2];
    uint32_t stageNext = 0;
    bool inflight = false; /* something has been enqueued since the last stream synchronisation */
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+   std::vector<std::vector<float>> widened; /* TEST SCAFFOLDING: int16 input widened for the twins (widen_i16), kept until the next sync */
+#endif
 
    std::vector<NfcConfig> configs;
    std::vector<StreamInfo> streams;
@@ -524,7 +546,7 @@ int launch_demod(nfcgpu_ctx *ctx, uint32_t config, NfcLaunch &L, uint64_t sample
 
    if (!exactOnly)
    {
-      hipLaunchKernelGGL(fixed ? nfc_demod_fixed_kernel : nfc_demod_kernel, dim3(lastBlock - firstBlock + 1), dim3(NFC_LANES), 0,
+      hipLaunchKernelGGL(fixed ? NFC_BY_LAYOUT(L.uniformStride, nfc_demod_fixed_kernel) : NFC_BY_LAYOUT(L.uniformStride, nfc_demod_kernel), dim3(lastBlock - firstBlock + 1), dim3(NFC_LANES), 0,
                          ctx->stream, ctx->dConfigs + config, L);
       HIP_TRY(ctx, hipGetLastError());
    }
@@ -532,7 +554,7 @@ int launch_demod(nfcgpu_ctx *ctx, uint32_t config, NfcLaunch &L, uint64_t sample
    /* stream blocks near their start / the clock wrap skip the kernel above and are handled by this one */
    if (exactPossible)
    {
-      hipLaunchKernelGGL(fixed ? nfc_demod_fixed_exact_kernel : nfc_demod_exact_kernel, dim3(lastBlock - firstBlock + 1),
+      hipLaunchKernelGGL(fixed ? NFC_BY_LAYOUT(L.uniformStride, nfc_demod_fixed_exact_kernel) : NFC_BY_LAYOUT(L.uniformStride, nfc_demod_exact_kernel), dim3(lastBlock - firstBlock + 1),
                          dim3(NFC_LANES), 0, ctx->stream, ctx->dConfigs + config, L);
       HIP_TRY(ctx, hipGetLastError());
    }
@@ -614,7 +636,9 @@ int grow(nfcgpu_ctx *ctx, nfcgpu_ctx::DevBuf &b, size_t bytes)
    return NFCGPU_OK;
 }
 
-/* the sequential kernels over a subset of slots (fallback of the time-parallel path) */
+/* the sequential kernels over a subset of slots (fallback of the time-parallel path). `stride` here and in everything below
+ * that takes one is the submission's sample layout (nfc_sample.hpp): the components per sample, 1 or 2, for floats - the value it
+ * has always been -, with NFC_SAMPLE_I16 set for int16 input */
 int launch_sequential(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedItem> &items, uint32_t stride)
 {
    if (items.empty())
@@ -636,7 +660,7 @@ int launch_sequential(nfcgpu_ctx *ctx, uint32_t config, const std::vector<Window
             const uint32_t n = it.count < head ? it.count : head;
             first.push_back(WindowedItem {it.slot, it.data, n});
             if (it.count > n)
-               rest.push_back(WindowedItem {it.slot, it.data + (size_t)n * stride * 4, it.count - n});
+               rest.push_back(WindowedItem {it.slot, it.data + (size_t)n * nfc_sample_bytes(stride), it.count - n});
          }
 
          int rc = launch_sequential(ctx, config, first, stride);
@@ -763,7 +787,7 @@ int run_in_blocks(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIt
          if (it.count > at)
          {
             const uint64_t left = it.count - at;
-            block.push_back(WindowedItem {it.slot, it.data + (size_t)at * stride * 4, (uint32_t)(left < blockSamples ? left : blockSamples)});
+            block.push_back(WindowedItem {it.slot, it.data + (size_t)at * nfc_sample_bytes(stride), (uint32_t)(left < blockSamples ? left : blockSamples)});
          }
       }
 
@@ -1022,7 +1046,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
    /* scan */
    ProfiledLaunch pl {nullptr, nullptr};
    record_span(ctx, ctx->timedScan, pl, true);
-   hipLaunchKernelGGL(nfc_scan_kernel, dim3((nChunks + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, A);
+   hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_scan_kernel), dim3((nChunks + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, A);
    HIP_TRY(ctx, hipGetLastError());
    record_span(ctx, ctx->timedScan, pl, false);
    ctx->stats.scan_samples += totalSamples;
@@ -1168,7 +1192,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
          const uint32_t listedNow = R.nChunks + R.nChunksMore;
 
-         hipLaunchKernelGGL(nfc_scan_kernel, dim3((listedNow + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, R);
+         hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_scan_kernel), dim3((listedNow + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, R);
          HIP_TRY(ctx, hipGetLastError());
       }
 
@@ -1179,7 +1203,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
          R.nChunks = alone;
          R.followChains = alone <= ctx->envelopeFollowMax ? 1u : 0u;
 
-         hipLaunchKernelGGL(nfc_envelope_kernel, dim3(alone), dim3(NFC_LANES), 0, ctx->stream, dCfg, R);
+         hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_envelope_kernel), dim3(alone), dim3(NFC_LANES), 0, ctx->stream, dCfg, R);
          HIP_TRY(ctx, hipGetLastError());
       }
 
@@ -1215,7 +1239,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
          ProfiledLaunch pp {nullptr, nullptr};
          record_span(ctx, ctx->timedPlanes, pp, true, ctx->low);
-         hipLaunchKernelGGL(nfc_scan_planes_kernel, dim3((uint32_t)((lanesOfIt + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->low, dCfg, P);
+         hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)((lanesOfIt + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->low, dCfg, P);
          HIP_TRY(ctx, hipGetLastError());
          record_span(ctx, ctx->timedPlanes, pp, false, ctx->low);
          HIP_TRY(ctx, hipEventRecord(ctx->joinEvent, ctx->low));
@@ -1264,7 +1288,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
          ProfiledLaunch pp {nullptr, nullptr};
          record_span(ctx, ctx->timedPlanes, pp, true);
-         hipLaunchKernelGGL(nfc_scan_planes_kernel, dim3((uint32_t)(((uint64_t)again * P.planesPerChunk + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->stream, dCfg, P);
+         hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)(((uint64_t)again * P.planesPerChunk + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->stream, dCfg, P);
          HIP_TRY(ctx, hipGetLastError());
          record_span(ctx, ctx->timedPlanes, pp, false);
       }
@@ -1311,7 +1335,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
       ProfiledLaunch pp {nullptr, nullptr};
       record_span(ctx, ctx->timedPlanes, pp, true);
-      hipLaunchKernelGGL(nfc_scan_planes_kernel, dim3((nPlaneLanes + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, P);
+      hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((nPlaneLanes + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, P);
       HIP_TRY(ctx, hipGetLastError());
       record_span(ctx, ctx->timedPlanes, pp, false);
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); /* (the chunk list is a local) */
@@ -1382,7 +1406,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
       ProfiledLaunch wl {nullptr, nullptr};
       record_span(ctx, ctx->timedWave, wl, true, on);
-      hipLaunchKernelGGL(nfc_wave_kernel, dim3(slotCount), dim3(NFC_LANES), 0, on, dCfg, L, A, carry ? 0u : 2u); /* a wave per lane */
+      hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_wave_kernel), dim3(slotCount), dim3(NFC_LANES), 0, on, dCfg, L, A, carry ? 0u : 2u); /* a wave per lane */
       record_span(ctx, ctx->timedWave, wl, false, on);
       HIP_TRY(ctx, hipGetLastError());
       ctx->stats.launches++;
@@ -1397,7 +1421,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
       ProfiledLaunch wl {nullptr, nullptr};
       record_span(ctx, ctx->timedWave, wl, true);
-      hipLaunchKernelGGL(nfc_wave_kernel, dim3(runLanes), dim3(NFC_LANES), 0, ctx->stream, dCfg, L, A, 1u); /* a wave per run-list entry */
+      hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_wave_kernel), dim3(runLanes), dim3(NFC_LANES), 0, ctx->stream, dCfg, L, A, 1u); /* a wave per run-list entry */
       record_span(ctx, ctx->timedWave, wl, false);
       HIP_TRY(ctx, hipGetLastError());
       ctx->stats.launches++;
@@ -2426,11 +2450,56 @@ int nfcgpu_stream_close(nfcgpu_ctx *ctx, uint32_t id)
    return rc;
 }
 
-int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *b)
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+namespace {
+
+/* TEST SCAFFOLDING, emulated build only. The CPU twins of the kernels (tests/hostsim) read floats and nothing else, so here the
+ * _fmt entry points widen an int16 buffer on the host - nfc_i16_to_float, the conversion the device loaders apply - and go on as
+ * NFCGPU_FMT_F32. What the emulated build therefore exercises of int16 input is the argument checks, the rate adoption and the
+ * equality of the conversion; what it does not: the device loaders (nfc_sample_at, the int16 row fetches of nfc_stage_tile,
+ * nfc_scan_body and nfc_planes_body), the slice offsets in bytes per sample and the staging sizes. Those run on the GPU only
+ * (tests/test_int16_input.py there). The floats live until the next nfcgpu_sync, as device-resident input has to. */
+const float *widen_i16(nfcgpu_ctx *ctx, const void *data, size_t values)
+{
+   ctx->widened.emplace_back(values ? values : 1);
+   std::vector<float> &to = ctx->widened.back();
+   for (size_t i = 0; i < values; i++)
+      to[i] = nfc_i16_to_float(((const int16_t *)data)[i]);
+   return to.data();
+}
+
+}
+#endif
+
+int nfcgpu_submit_batch_fmt(nfcgpu_ctx *ctx, const nfcgpu_batch *b, uint32_t format)
 {
    if (!ctx || !b || !b->stream_ids || !b->data || !b->n_samples || (b->stride != 1 && b->stride != 2) ||
-       (b->location != NFCGPU_LOC_HOST && b->location != NFCGPU_LOC_DEVICE))
+       (b->location != NFCGPU_LOC_HOST && b->location != NFCGPU_LOC_DEVICE) || (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16))
       return NFCGPU_EINVAL;
+
+   /* the sample layout of the batch (nfc_sample.hpp): b->stride itself for floats */
+   const uint32_t layout = b->stride | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u);
+
+   if (format == NFCGPU_FMT_I16)
+   {
+      /* rows are read as int16 or as pairs of them: every pointer has to be aligned to a sample */
+      for (uint32_t i = 0; i < b->n_streams; i++)
+      {
+         if (((uintptr_t)b->data[i] % nfc_sample_bytes(layout)) != 0)
+            return fail(ctx, NFCGPU_EINVAL, "int16 data pointers must be multiples of the sample size (2 bytes magnitude, 4 bytes IQ)");
+      }
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+      /* (test scaffolding: see widen_i16) */
+      std::vector<const void *> rows(b->n_streams);
+      for (uint32_t i = 0; i < b->n_streams; i++)
+         rows[i] = b->data[i] ? widen_i16(ctx, b->data[i], (size_t)b->n_samples[i] * b->stride) : nullptr;
+
+      nfcgpu_batch wide = *b;
+      wide.data = rows.data();
+      return nfcgpu_submit_batch_fmt(ctx, &wide, NFCGPU_FMT_F32);
+#endif
+   }
 
    if (b->n_streams == 0)
       return NFCGPU_OK;
@@ -2475,7 +2544,7 @@ int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *b)
 
       ctx->streams[id].listed = true;
       ctx->hWorks[id].count = b->n_samples[i];
-      hostBytes += (size_t)b->n_samples[i] * b->stride * 4;
+      hostBytes += (size_t)b->n_samples[i] * nfc_sample_bytes(layout);
       lo = id < lo ? id : lo;
       hi = id > hi ? id : hi;
    }
@@ -2533,9 +2602,9 @@ int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *b)
    {
       const uint32_t id = b->stream_ids[i];
       NfcWork &w = ctx->hWorks[id];
-      const size_t bytes = (size_t)b->n_samples[i] * b->stride * 4;
+      const size_t bytes = (size_t)b->n_samples[i] * nfc_sample_bytes(layout);
 
-      w.stride = b->stride;
+      w.stride = layout;
 
       if (b->location == NFCGPU_LOC_HOST)
       {
@@ -2575,7 +2644,7 @@ int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *b)
 
          if (windowed_eligible(ctx, c, items))
          {
-            rc = run_windowed(ctx, c, items, b->stride);
+            rc = run_windowed(ctx, c, items, layout);
             if (rc)
             {
                clearWorks();
@@ -2629,7 +2698,7 @@ int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *b)
 
       NfcLaunch L = base_launch(ctx);
       L.works = ctx->dWorks;
-      L.uniformStride = b->stride; /* one sample format per batch */
+      L.uniformStride = layout; /* one sample format per batch */
       L.firstSlot = first;
       L.slotCount = last - first + 1;
 
@@ -2655,7 +2724,17 @@ int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *b)
    return NFCGPU_OK;
 }
 
+int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *b)
+{
+   return nfcgpu_submit_batch_fmt(ctx, b, NFCGPU_FMT_F32);
+}
+
 int nfcgpu_submit(nfcgpu_ctx *ctx, uint32_t id, const float *data, uint32_t n, uint32_t stride, uint32_t sampleRate)
+{
+   return nfcgpu_submit_fmt(ctx, id, data, n, stride, sampleRate, NFCGPU_FMT_F32);
+}
+
+int nfcgpu_submit_fmt(nfcgpu_ctx *ctx, uint32_t id, const void *data, uint32_t n, uint32_t stride, uint32_t sampleRate, uint32_t format)
 {
    const void *ptr = data;
    nfcgpu_batch b;
@@ -2667,19 +2746,41 @@ int nfcgpu_submit(nfcgpu_ctx *ctx, uint32_t id, const float *data, uint32_t n, u
    b.stream_ids = &id;
    b.data = &ptr;
    b.n_samples = &n;
-   return nfcgpu_submit_batch(ctx, &b);
+   return nfcgpu_submit_batch_fmt(ctx, &b, format);
 }
 
 int nfcgpu_magnitude(nfcgpu_ctx *ctx, const float *iq, uint64_t n, float *out, uint32_t location)
 {
-   if (!ctx || !iq || !out || (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE))
+   return nfcgpu_magnitude_fmt(ctx, iq, n, out, location, NFCGPU_FMT_F32);
+}
+
+int nfcgpu_magnitude_fmt(nfcgpu_ctx *ctx, const void *iq, uint64_t n, float *out, uint32_t location, uint32_t format)
+{
+   if (!ctx || !iq || !out || (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE) || (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16))
       return NFCGPU_EINVAL;
+
+   const bool i16 = format == NFCGPU_FMT_I16;
+
+   if (i16 && ((uintptr_t)iq % 4u) != 0)
+      return fail(ctx, NFCGPU_EINVAL, "int16 IQ must be 4-byte aligned");
+
    if (n == 0)
       return NFCGPU_OK;
 
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+   /* (test scaffolding: see widen_i16; the call waits, so the floats go at once) */
+   if (i16)
+   {
+      const float *wide = widen_i16(ctx, iq, (size_t)n * 2);
+      const int rc = nfcgpu_magnitude_fmt(ctx, wide, n, out, location, NFCGPU_FMT_F32);
+      ctx->widened.pop_back();
+      return rc;
+   }
+#endif
+
    HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-   const float2 *src = (const float2 *)iq;
+   const void *src = iq;
    float *dst = out;
    nfcgpu_ctx::StageSlot *slot = nullptr;
 
@@ -2688,14 +2789,14 @@ int nfcgpu_magnitude(nfcgpu_ctx *ctx, const float *iq, uint64_t n, float *out, u
    if (location == NFCGPU_LOC_HOST)
    {
       /* staging area: IQ first, magnitudes behind it */
-      const size_t inBytes = (size_t)n * 8, outBytes = (size_t)n * 4;
+      const size_t inBytes = (size_t)n * (i16 ? 4 : 8), outBytes = (size_t)n * 4;
       int rc = stage_acquire(ctx, inBytes + outBytes, &slot);
       if (rc)
          return rc;
 
       std::memcpy(slot->h, iq, inBytes);
       HIP_TRY(ctx, hipMemcpyAsync(slot->d, slot->h, inBytes, hipMemcpyHostToDevice, ctx->stream));
-      src = (const float2 *)slot->d;
+      src = slot->d;
       dst = (float *)(slot->d + inBytes);
    }
 
@@ -2703,17 +2804,25 @@ int nfcgpu_magnitude(nfcgpu_ctx *ctx, const float *iq, uint64_t n, float *out, u
    const uint64_t wanted = (n + threads - 1) / threads;
    const uint32_t grid = (uint32_t)(wanted < 16384 ? wanted : 16384);
 
-   hipLaunchKernelGGL(nfc_magnitude_kernel, dim3(grid), dim3(threads), 0, ctx->stream, src, dst, n);
+#ifndef NFCGPU_EMULATED_TEST_BUILD
+   if (i16)
+      hipLaunchKernelGGL(nfc_magnitude_kernel_i16, dim3(grid), dim3(threads), 0, ctx->stream, (const NfcIq16 *)src, dst, n);
+   else
+#endif
+      hipLaunchKernelGGL(nfc_magnitude_kernel, dim3(grid), dim3(threads), 0, ctx->stream, (const float2 *)src, dst, n);
    HIP_TRY(ctx, hipGetLastError());
 
+   /* (the magnitudes sit behind the IQ in both halves of the slot) */
+   const size_t outAt = (size_t)n * (i16 ? 4 : 8);
+
    if (location == NFCGPU_LOC_HOST)
-      HIP_TRY(ctx, hipMemcpyAsync(slot->h + (size_t)n * 8, dst, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(slot->h + outAt, dst, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
 
    /* the result goes back to the caller: this entry point waits */
    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
    if (location == NFCGPU_LOC_HOST)
-      std::memcpy(out, slot->h + (size_t)n * 8, (size_t)n * 4);
+      std::memcpy(out, slot->h + outAt, (size_t)n * 4);
 
    return NFCGPU_OK;
 }
@@ -2998,15 +3107,43 @@ int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t
 int nfcgpu_submit_uniform(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, const void *base, uint64_t pitch, uint32_t n,
                           uint32_t stride, uint32_t location, uint32_t sampleRate)
 {
-   if (!ctx || !base || (stride != 1 && stride != 2) || count == 0 ||
-       (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE) || (count > 1 && pitch < (uint64_t)n * stride * 4))
+   return nfcgpu_submit_uniform_fmt(ctx, first, count, base, pitch, n, stride, location, sampleRate, NFCGPU_FMT_F32);
+}
+
+int nfcgpu_submit_uniform_fmt(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, const void *base, uint64_t pitch, uint32_t n,
+                              uint32_t components, uint32_t location, uint32_t sampleRate, uint32_t format)
+{
+   if (!ctx || !base || (components != 1 && components != 2) || count == 0 || (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16) ||
+       (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE))
+      return NFCGPU_EINVAL;
+
+   /* the sample layout of the rows (nfc_sample.hpp): the components per sample themselves for floats */
+   const uint32_t stride = components | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u);
+   const uint32_t sampleBytes = nfc_sample_bytes(stride);
+
+   if (count > 1 && pitch < (uint64_t)n * sampleBytes)
       return NFCGPU_EINVAL;
    if ((uint64_t)first + count > ctx->maxStreams)
       return fail(ctx, NFCGPU_ESTREAM, "stream range out of bounds");
 
-   /* rows are read as float2 (IQ) or float: base and pitch have to be aligned to a sample */
-   if (((uintptr_t)base % (4u * stride)) != 0 || (count > 1 && (pitch % (4u * stride)) != 0))
-      return fail(ctx, NFCGPU_EINVAL, "base and pitch must be multiples of the sample size (4 bytes magnitude, 8 bytes IQ)");
+   /* rows are read as float2 (IQ) or float, as pairs of int16 or int16: base and pitch have to be aligned to a sample */
+   if (((uintptr_t)base % sampleBytes) != 0 || (count > 1 && (pitch % sampleBytes) != 0))
+      return fail(ctx, NFCGPU_EINVAL, format == NFCGPU_FMT_I16 ? "base and pitch must be multiples of the sample size (2 bytes int16 magnitude, 4 bytes int16 IQ)"
+                                                                : "base and pitch must be multiples of the sample size (4 bytes magnitude, 8 bytes IQ)");
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+   /* (test scaffolding: see widen_i16) */
+   if (format == NFCGPU_FMT_I16)
+   {
+      const size_t row = (size_t)n * components;
+      ctx->widened.emplace_back(row * count + 2);
+      float *wide = ctx->widened.back().data();
+      for (uint32_t r = 0; r < count; r++)
+         for (size_t i = 0; i < row; i++)
+            wide[(size_t)r * row + i] = nfc_i16_to_float(((const int16_t *)((const uint8_t *)base + (size_t)r * pitch))[i]);
+      return nfcgpu_submit_uniform_fmt(ctx, first, count, wide, row * 4, n, components, location, sampleRate, NFCGPU_FMT_F32);
+   }
+#endif
 
    HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -3040,7 +3177,7 @@ int nfcgpu_submit_uniform(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, const
 
    if (location == NFCGPU_LOC_HOST)
    {
-      const size_t row = (size_t)n * stride * 4;
+      const size_t row = (size_t)n * sampleBytes;
       devPitch = (row + 255) & ~(size_t)255;
 
       int rc = stage_acquire(ctx, devPitch * count, &slot);
@@ -3081,6 +3218,9 @@ int nfcgpu_sync(nfcgpu_ctx *ctx)
    HIP_TRY(ctx, hipSetDevice(ctx->device));
    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
    ctx->inflight = false;
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+   ctx->widened.clear(); /* (test scaffolding: widen_i16) */
+#endif
 
    if (!ctx->timedWave.empty() || !ctx->timedPlanes.empty())
       (void)hipStreamSynchronize(ctx->side); /* (carry lanes run beside the windows) */

@@ -14,6 +14,9 @@ LIB_PATH = os.environ.get("NFCGPU_LIB", os.path.join(HERE, "libnfcgpu.so"))
 
 TECH_A, TECH_B, TECH_F, TECH_V = 1, 2, 4, 8
 LOC_HOST, LOC_DEVICE = 0, 1
+# sample formats of the decoder's input (NFCGPU_FMT_*): float32, or the little-endian int16 PCM capture files hold,
+# value = v / 32768, converted by the kernels as they load
+FMT_F32, FMT_I16 = 0, 1
 
 FRAME_CARRIER_OFF, FRAME_CARRIER_ON, FRAME_POLL, FRAME_LISTEN = 0x100, 0x101, 0x102, 0x103
 
@@ -145,6 +148,10 @@ def load_library(path=LIB_PATH):
     lib.nfcgpu_submit_batch.argtypes = [vp, P(Batch)]
     lib.nfcgpu_submit_uniform.argtypes = [vp, u32, u32, vp, u64, u32, u32, u32, u32]
     lib.nfcgpu_magnitude.argtypes = [vp, vp, u64, vp, u32]
+    lib.nfcgpu_submit_fmt.argtypes = [vp, u32, vp, u32, u32, u32, u32]
+    lib.nfcgpu_submit_batch_fmt.argtypes = [vp, P(Batch), u32]
+    lib.nfcgpu_submit_uniform_fmt.argtypes = [vp, u32, u32, vp, u64, u32, u32, u32, u32, u32]
+    lib.nfcgpu_magnitude_fmt.argtypes = [vp, vp, u64, vp, u32, u32]
     lib.nfcgpu_resample_radio.argtypes = [vp, vp, u64, u32, u32, vp, u64, u32, vp, u32]
     lib.nfcgpu_spectrum_default_params.argtypes = [P(SpectrumParams)]
     lib.nfcgpu_spectrum_default_params.restype = None
@@ -235,30 +242,47 @@ class NfcGpu:
     def close_stream(self, stream):
         self._check(self.lib.nfcgpu_stream_close(self.ctx, stream))
 
-    def submit(self, stream, samples, sample_rate, stride=1):
-        """samples: contiguous float32 numpy array (host)."""
+    def submit(self, stream, samples, sample_rate, stride=1, fmt=FMT_F32):
+        """samples: contiguous numpy array (host) of stride values per sample: float32, or with fmt=FMT_I16 int16 PCM.
+        The format is what `fmt` says, never the array's dtype: the bytes are read as that format."""
         n = samples.size // stride
-        self._check(self.lib.nfcgpu_submit(self.ctx, stream, samples.ctypes.data, n, stride, sample_rate))
+        if fmt == FMT_F32:
+            self._check(self.lib.nfcgpu_submit(self.ctx, stream, samples.ctypes.data, n, stride, sample_rate))
+        else:
+            self._check(self.lib.nfcgpu_submit_fmt(self.ctx, stream, samples.ctypes.data, n, stride, sample_rate, fmt))
 
-    def submit_batch(self, stream_ids, pointers, counts, sample_rate, stride=1, location=LOC_HOST):
+    def submit_batch(self, stream_ids, pointers, counts, sample_rate, stride=1, location=LOC_HOST, fmt=FMT_F32):
         n = len(stream_ids)
         ids = (ctypes.c_uint32 * n)(*stream_ids)
         ptrs = (ctypes.c_void_p * n)(*pointers)
         cnts = (ctypes.c_uint32 * n)(*counts)
         b = Batch(n, stride, location, sample_rate, ids, ptrs, cnts)
-        self._check(self.lib.nfcgpu_submit_batch(self.ctx, ctypes.byref(b)))
+        if fmt == FMT_F32:
+            self._check(self.lib.nfcgpu_submit_batch(self.ctx, ctypes.byref(b)))
+        else:
+            self._check(self.lib.nfcgpu_submit_batch_fmt(self.ctx, ctypes.byref(b), fmt))
 
-    def submit_uniform(self, first, count, base_ptr, pitch_bytes, n_samples, sample_rate, stride=1, location=LOC_DEVICE):
-        self._check(self.lib.nfcgpu_submit_uniform(self.ctx, first, count, base_ptr, pitch_bytes, n_samples, stride,
-                                                   location, sample_rate))
+    def submit_uniform(self, first, count, base_ptr, pitch_bytes, n_samples, sample_rate, stride=1, location=LOC_DEVICE, fmt=FMT_F32):
+        if fmt == FMT_F32:
+            self._check(self.lib.nfcgpu_submit_uniform(self.ctx, first, count, base_ptr, pitch_bytes, n_samples, stride,
+                                                       location, sample_rate))
+        else:
+            self._check(self.lib.nfcgpu_submit_uniform_fmt(self.ctx, first, count, base_ptr, pitch_bytes, n_samples, stride,
+                                                           location, sample_rate, fmt))
 
-    def magnitude(self, iq):
-        """|IQ| of an interleaved float32 numpy array (host memory), computed on the device with the reference's
-        roundings."""
-        iq = np.ascontiguousarray(iq, dtype=np.float32)
+    def magnitude(self, iq, fmt=FMT_F32):
+        """|IQ| of an interleaved numpy array (host memory) - float32, or with fmt=FMT_I16 int16 PCM, converted v / 32768 -
+        computed on the device with the reference's roundings."""
+        if fmt == FMT_F32:
+            iq = np.ascontiguousarray(iq, dtype=np.float32)
+            n = iq.size // 2
+            out = np.empty(n, dtype=np.float32)
+            self._check(self.lib.nfcgpu_magnitude(self.ctx, iq.ctypes.data, n, out.ctypes.data, LOC_HOST))
+            return out
+        iq = np.ascontiguousarray(iq, dtype=np.int16) if fmt == FMT_I16 else np.ascontiguousarray(iq)
         n = iq.size // 2
         out = np.empty(n, dtype=np.float32)
-        self._check(self.lib.nfcgpu_magnitude(self.ctx, iq.ctypes.data, n, out.ctypes.data, LOC_HOST))
+        self._check(self.lib.nfcgpu_magnitude_fmt(self.ctx, iq.ctypes.data, n, out.ctypes.data, LOC_HOST, fmt))
         return out
 
     def resample_radio(self, buffers, capacity_pairs=None):
