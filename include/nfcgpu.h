@@ -146,6 +146,14 @@ typedef struct nfcgpu_stats
     * intervals (the carry lanes of a pass run on a second HIP stream beside the speculative lanes, so wave_ms, the sum of
     * the launch durations, counts the overlap twice). Profiling on; measured from the reset on. */
    double wave_busy_ms;
+   /* pipelined submissions (read through nfcgpu_stats_get_sized): submissions whose front - scan, seam rounds, planes - ran under
+    * the pending tail of the submission before, and streams whose front was walked again because the state the finish left in
+    * their slot was not the one that front had started from (exact or not taken) */
+   uint64_t pipelined_submissions;
+   uint64_t pipeline_refronts;
+   /* ... and streams of pipelined submissions that ended on an edge time zeroed by a carrier frame where the shadow held the
+    * tracker's time: the one expected difference, put right in the front's records without a walk (not counted above) */
+   uint64_t pipeline_zeroed_edges;
 } nfcgpu_stats;
 
 #define NFCGPU_STATS_SIZE_V2 104u /* bytes of nfcgpu_stats up to and including scan_repairs: what nfcgpu_stats_get writes */
@@ -174,8 +182,10 @@ int nfcgpu_stream_close(nfcgpu_ctx *ctx, uint32_t stream_id);
 /* Submissions are asynchronous: the calls return once the work is enqueued on the context's HIP stream. Host memory
  * (NFCGPU_LOC_HOST, nfcgpu_submit) has been copied into a pinned staging buffer by then and is never retained; device
  * memory (NFCGPU_LOC_DEVICE) is read in place and must stay as it is until the next nfcgpu_sync / nfcgpu_poll /
- * nfcgpu_flush / nfcgpu_pending of the context. (Long grid-aligned submissions that take the time-parallel path are
- * complete when the call returns.) */
+ * nfcgpu_flush / nfcgpu_pending of the context. That holds for every submission: a long grid-aligned one that takes the
+ * time-parallel path through nfcgpu_submit_uniform returns once its first decode pass is queued; its last passes and the finish
+ * stay pending on the context, and the next such submission of the same streams walks its front end beside them. Every other
+ * call on the context completes what is pending before it does anything else, and returns an error met there. */
 int nfcgpu_submit(nfcgpu_ctx *ctx, uint32_t stream_id, const float *data, uint32_t n_samples, uint32_t stride, uint32_t sample_rate);
 int nfcgpu_submit_batch(nfcgpu_ctx *ctx, const nfcgpu_batch *batch);
 /* streams first..first+count-1; stream i reads n_samples*stride floats at base + i*pitch_bytes */

@@ -18,6 +18,7 @@
 #include <deque>
 #include <algorithm>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -113,6 +114,197 @@ NFC_SPECTRUM_KERNEL(2048)
 NFC_SPECTRUM_KERNEL(4096)
 #undef NFC_SPECTRUM_KERNEL
 
+/* ---- helper kernels of pipelined submissions (run_windowed): a thread per stream of the submission ----
+ * The front of a submission (scan, seam rounds, planes) reads of a stream's slot the front-end state its first chunk starts from:
+ * clock, pulse counter, envelope, filter, deviation, average, edge peak, edge time and the carrier zone (nfc_scan_begin, and the
+ * edge time once more in nfc_seams_kernel). While the submission before is still in its tail the finish has not written those
+ * yet - but the front end is a function of the samples: once that submission's seam rounds are over, the end of its last chunk
+ * is the state its finish will write. nfc_shadow_kernel forms it; nfc_shadow_compare_kernel holds it against what the finish
+ * really wrote, bit for bit on exactly those fields (the carrier times as the zone the front derives from them, which is all it
+ * reads of them), and counts the streams that differ: exact or not taken.
+ *
+ * One difference is expected and is put right without a second walk. The decoder zeroes its copy of the edge time when it emits a
+ * carrier frame (nfc_scan_begin's note), so a stream whose last carrier frame came after the tracker last moved ends with 0 where
+ * its shadow holds the tracker's time T. Nothing a walk computes depends on the time it starts with: the tracker overwrites it with
+ * clocks of the new submission's own samples, and until then the start value is only handed on - into the chunks' inherited times
+ * (chunkEdge), into the start of a chunk that is walked again from its predecessor's end and from there into that walk's
+ * records - and tested for equality against values of the same kind (nfc_seams_check, nfc_scan_adopt). T is a clock of an
+ * earlier sample and 0 is not a clock of this submission either (the path keeps clear of the clock's wrap), so neither can
+ * equal a time the tracker sets during the submission: every one of those tests falls the same way with 0 as with T, and the
+ * records of the walk from 0 are the records at hand with T replaced by 0 wherever a record holds T as a known time.
+ * nfc_shadow_rename_kernel does that for the streams the comparison found to differ in this way and in nothing else. */
+struct NfcShadowArgs
+{
+   const NfcScanJob *jobs;
+   uint32_t nJobs;
+   const NfcScanSeam *seams;      /* shadow kernel: the records of the submission whose end is formed */
+   const uint32_t *chunkEdge;
+   const NfcStreamState *from;    /* shadow kernel: what that submission's front started from (the slots, or the shadows themselves) */
+   NfcStreamState *shadow;        /* [maxStreams] */
+   const NfcStreamState *real;    /* compare kernel: the slots */
+   uint32_t *ctl;                 /* compare kernel: [0] streams that differ otherwise than by a zeroed edge time, [1..9] streams that differ in clock, pulse counter,
+                                     envelope, n1, deviation, average, edge peak, edge time, carrier zone, [10] streams with a zeroed edge time alone;
+                                     [16 + j]: stream j of the submission 0 same, 1 zeroed edge time alone, 2 differs */
+   NfcScanPoint *points;          /* rename kernel: the records of the front that started from the shadows */
+   NfcScanSeam *renameSeams;
+   uint32_t *renameEdge;
+   uint32_t spoil;                /* shadow kernel, test switch: 1 + the slot whose shadow is spoilt (0: none) */
+};
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+#define NFC_PIPE_FN static inline
+#define NFC_PIPE_COUNT(p) (++*(p))
+#else
+#define NFC_PIPE_FN static __device__ __forceinline__
+#define NFC_PIPE_COUNT(p) atomicAdd((p), 1u)
+#endif
+
+NFC_PIPE_FN uint32_t nfc_pipe_bits(float v)
+{
+   uint32_t u;
+   __builtin_memcpy(&u, &v, 4);
+   return u;
+}
+
+/* the carrier zone a walk starts in (nfc_scan_begin) */
+NFC_PIPE_FN uint32_t nfc_pipe_zone(const NfcStreamState &s)
+{
+   return s.carrierOn ? 1u : (s.carrierOff ? 2u : 0u);
+}
+
+NFC_PIPE_FN void nfc_shadow_write(const NfcShadowArgs &S, uint32_t j)
+{
+   const NfcScanJob &job = S.jobs[j];
+
+   if (job.chunks == 0u)
+      return;
+
+   const uint32_t last = job.firstChunk + job.chunks - 1u;
+   const NfcScanPoint &end = S.seams[last].end;
+
+   NfcStreamState s = S.from[job.slot];
+
+   s.clock += job.count;
+   s.pulseFilter = end.pulseFilter;
+   s.env = end.env;
+   s.n1 = end.n1;
+   s.mdev = end.mdev;
+   s.avg = end.avg;
+   s.edgePeak = end.edgePeak;
+   /* the edge tracker's time: the walk's own where it has set one (NFC_ZONE_EDGE_KNOWN of nfc_scan.hpp), else the one the last chunk
+    * inherited. The decoder's copy is zeroed by a carrier frame (nfc_scan_begin's note): a stream that emitted one after the
+    * tracker last moved differs here, is found by the comparison and has the time put right in its records (nfc_shadow_rename). */
+   s.edgeTime = (end.zone & 0x100u) ? end.edgeTime : S.chunkEdge[last];
+   s.carrierOn = (end.zone & 0xFFu) == 1u ? 1u : 0u;
+   s.carrierOff = (end.zone & 0xFFu) == 2u ? 1u : 0u;
+
+   if (S.spoil == job.slot + 1u)
+      s.avg = -s.avg - 1.0f;
+
+   S.shadow[job.slot] = s;
+}
+
+NFC_PIPE_FN void nfc_shadow_compare(const NfcShadowArgs &S, uint32_t j)
+{
+   const NfcStreamState &a = S.real[S.jobs[j].slot], &b = S.shadow[S.jobs[j].slot];
+
+   const bool differ[9] = {a.clock != b.clock,
+                           a.pulseFilter != b.pulseFilter,
+                           nfc_pipe_bits(a.env) != nfc_pipe_bits(b.env),
+                           nfc_pipe_bits(a.n1) != nfc_pipe_bits(b.n1),
+                           nfc_pipe_bits(a.mdev) != nfc_pipe_bits(b.mdev),
+                           nfc_pipe_bits(a.avg) != nfc_pipe_bits(b.avg),
+                           nfc_pipe_bits(a.edgePeak) != nfc_pipe_bits(b.edgePeak),
+                           a.edgeTime != b.edgeTime,
+                           nfc_pipe_zone(a) != nfc_pipe_zone(b)};
+   bool any = false;
+
+   for (int i = 0; i < 9; i++)
+   {
+      if (differ[i])
+         NFC_PIPE_COUNT(S.ctl + 1 + i);
+      any = any || differ[i];
+   }
+
+   const bool zeroed = differ[7] && !(differ[0] || differ[1] || differ[2] || differ[3] || differ[4] || differ[5] || differ[6] || differ[8]) && a.edgeTime == 0u;
+
+   if (any)
+      NFC_PIPE_COUNT(zeroed ? S.ctl + 10 : S.ctl);
+
+   S.ctl[16 + j] = any ? (zeroed ? 1u : 2u) : 0u;
+}
+
+/* thread `lane` of `lanes` for stream j: the shadow's edge time becomes 0 wherever a record of the stream's front holds it as a known time */
+NFC_PIPE_FN void nfc_shadow_rename(const NfcShadowArgs &S, uint32_t j, uint32_t lane, uint32_t lanes)
+{
+   if (S.ctl[16 + j] != 1u)
+      return;
+
+   const NfcScanJob &job = S.jobs[j];
+   const uint32_t was = S.shadow[job.slot].edgeTime;
+
+   for (uint32_t k = lane; k < job.chunks; k += lanes)
+   {
+      NfcScanSeam &s = S.renameSeams[job.firstChunk + k];
+      if ((s.start.zone & 0x100u) && s.start.edgeTime == was)
+         s.start.edgeTime = 0u;
+      if ((s.end.zone & 0x100u) && s.end.edgeTime == was)
+         s.end.edgeTime = 0u;
+      if (S.renameEdge[job.firstChunk + k] == was)
+         S.renameEdge[job.firstChunk + k] = 0u;
+   }
+
+   const uint32_t nPoints = job.count / NFC_SCAN_POINT + 1u;
+
+   for (uint32_t i = lane; i < nPoints; i += lanes)
+   {
+      NfcScanPoint &p = S.points[job.firstPoint + i];
+      if ((p.zone & 0x100u) && p.edgeTime == was)
+         p.edgeTime = 0u;
+   }
+}
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+void nfc_shadow_kernel(NfcShadowArgs S)
+{
+   for (uint32_t j = 0; j < S.nJobs; j++)
+      nfc_shadow_write(S, j);
+}
+
+void nfc_shadow_compare_kernel(NfcShadowArgs S)
+{
+   for (uint32_t j = 0; j < S.nJobs; j++)
+      nfc_shadow_compare(S, j);
+}
+
+void nfc_shadow_rename_kernel(NfcShadowArgs S)
+{
+   for (uint32_t j = 0; j < S.nJobs; j++)
+      nfc_shadow_rename(S, j, 0u, 1u);
+}
+#else
+__global__ void nfc_shadow_kernel(NfcShadowArgs S)
+{
+   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+   if (j < S.nJobs)
+      nfc_shadow_write(S, j);
+}
+
+__global__ void nfc_shadow_compare_kernel(NfcShadowArgs S)
+{
+   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+   if (j < S.nJobs)
+      nfc_shadow_compare(S, j);
+}
+
+/* (a workgroup per stream) */
+__global__ void nfc_shadow_rename_kernel(NfcShadowArgs S)
+{
+   if (blockIdx.x < S.nJobs)
+      nfc_shadow_rename(S, blockIdx.x, threadIdx.x, blockDim.x);
+}
+#endif
+
 namespace {
 
 constexpr uint32_t kMaxConfigs = 256; /* distinct decoder configurations in use at once (1.5 KB each on the device) */
@@ -154,6 +346,8 @@ struct ProfiledLaunch
    hipEvent_t start;
    hipEvent_t stop;
 };
+
+struct WindowedTail;
 
 }
 
@@ -251,6 +445,25 @@ struct nfcgpu_ctx
                                       (thousands of lanes reading 32768-sample chunks a cache line each: 79 -> 122 ms per step of the headline,
                                       profiles/r04/ab_envelope) - and was given lists of at most 64 */
    DevBuf wPlanesStale;            /* NfcScanArgs::planesStale */
+
+   /* ---- pipelined submissions (run_windowed): the front of a submission under the tail of the one before ---- */
+   bool pipeline = true;           /* NFCGPU_PIPELINE=0: every submission is complete when its call returns */
+   WindowedTail *tail = nullptr; /* the pending tail: every entry point completes it first (settle_tail) */
+   hipStream_t front = nullptr;    /* the stream of a front that runs under a tail (the planes stay on `low`) */
+   hipEvent_t frontEvent = nullptr, planesFork = nullptr, planesJoin = nullptr;
+   DevBuf otherSet[13];            /* the second set of the buffers a front writes and a tail still reads (swap_front_sets), allocated when a
+                                      submission first finds a tail pending: about as much again as the first, nearly all of it planes */
+   DevBuf wShadow, wShadowCtl;     /* NfcShadowArgs::shadow, ::ctl */
+   bool noSecondSet = false;       /* the device could not give the second set: no overlap for this context */
+   bool growingSecond = false;
+   bool deferOK = false;           /* the submission at hand may leave its tail pending (nfcgpu_submit_uniform) */
+   bool dumpWindows = false;       /* NFCGPU_DUMP_WINDOWS is set (tuning build) */
+   bool pipelineReport = false;    /* NFCGPU_PIPELINE_REPORT is set (tuning build): a line on stderr per comparison of shadows and slots */
+   uint32_t spoilShadow = 0;       /* test switch of the tuning / emulated builds (NFCGPU_TEST_SPOIL_SHADOW): NfcShadowArgs::spoil */
+   uint32_t *tailHost = nullptr;   /* pinned words of the read-backs: [0] chain "again", [1] run list length, [2..3] staging sink control, [16..31] shadow comparison */
+   uint32_t *frontHost = nullptr;  /* ... of the front: [0..2] repair counts of a round, [4] stale plane chunks */
+   NfcScanJob *tailJobs = nullptr; /* pinned: the job table as the finish left it */
+   size_t tailJobsBytes = 0;
    uint32_t planesBeside = 1;      /* the walk that writes a large submission's planes runs on the side stream beside the rounds of second walks that follow the
                                       first (NFCGPU_PLANES_BESIDE; 0: after them, as until round 5) */
    uint32_t planesBesidePiece = 2048; /* ... samples per lane of that walk, from the stored points (NFCGPU_PLANES_BESIDE_PIECE; 0: a lane per chunk, from its start).
@@ -595,6 +808,12 @@ int grow(nfcgpu_ctx *ctx, nfcgpu_ctx::DevBuf &b, size_t bytes)
       if (&b == &ctx->wPlanes && bytes > std::strtoull(limit, nullptr, 10))
          return fail(ctx, NFCGPU_ENOMEM, "device allocation for the time-parallel path failed (test limit)");
    }
+   if (const char *limit = std::getenv("NFCGPU_TEST_ALLOC_LIMIT_SECOND"))
+   {
+      /* (... more than this for the planes of the second buffer set of pipelined submissions) */
+      if (ctx->growingSecond && &b == &ctx->wPlanes && bytes > std::strtoull(limit, nullptr, 10))
+         return fail(ctx, NFCGPU_ENOMEM, "device allocation for the time-parallel path failed (test limit)");
+   }
    if (const char *limit = std::getenv("NFCGPU_TEST_ALLOC_LIMIT_LANES"))
    {
       /* (the same for a buffer that is grown elsewhere in run_windowed: the lanes' decoder states) */
@@ -603,10 +822,11 @@ int grow(nfcgpu_ctx *ctx, nfcgpu_ctx::DevBuf &b, size_t bytes)
    }
 #endif
 
-   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-
    if (b.ptr)
+   {
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       (void)hipFree(b.ptr);
+   }
 
    b.ptr = nullptr;
    b.bytes = 0;
@@ -720,6 +940,10 @@ int launch_sequential(nfcgpu_ctx *ctx, uint32_t config, const std::vector<Window
    return NFCGPU_OK;
 }
 
+uint32_t tail_ahead(const nfcgpu_ctx *ctx, uint32_t slot);
+int settle_tail(nfcgpu_ctx *ctx);
+void stage_release(nfcgpu_ctx *ctx, nfcgpu_ctx::StageSlot *slot);
+
 /* may these streams take the time-parallel path for this submission? (one configuration, one sample format) */
 bool windowed_eligible(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedItem> &items)
 {
@@ -733,7 +957,9 @@ bool windowed_eligible(nfcgpu_ctx *ctx, uint32_t config, const std::vector<Windo
 
       /* stay clear of the 32-bit wrap of the sample clock: the lanes number their rings from their own first sample
        * and never take the exact-modulo route (a fresh stream, clock 0xFFFFFFFF, is handled by its carry lane) */
-      const uint32_t clock = ctx->streams[it.slot].clock;
+      uint32_t clock = ctx->streams[it.slot].clock;
+      if (const uint32_t ahead = tail_ahead(ctx, it.slot))
+         clock += ahead; /* (the mirror follows when the pending tail completes: the clock that submission will leave) */
       if (clock != 0xFFFFFFFFu && (uint64_t)clock + it.count + 4096u >= 0xFFFFFFFFull)
          return false;
    }
@@ -798,702 +1024,211 @@ int run_in_blocks(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIt
    return rc;
 }
 
-/* One submission of `items` (all of configuration `config`, `stride` floats per sample, data resident on the device)
- * through scan -> windows -> windowed decode -> chain -> finish; streams the path cannot vouch for (samples off the
- * int16 grid, a seam that did not verify, no settled chain) are then decoded sequentially from their untouched state. */
-int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedItem> &items, uint32_t stride)
+/* ------------------------------------------------------------------------------------------ */
+/* the tail of a time-parallel submission                                                      */
+/* ------------------------------------------------------------------------------------------ */
+
+/* What is left of a submission once its first decode pass and the chain kernel behind it are queued: the later passes - a few
+ * thousand lanes, then a few dozen, each pass as long as its longest lane at one wave's speed -, the final lanes, the finish and
+ * the job read-back. The device is all but idle under it, so it is kept as a small resumable object: a submission may return to
+ * its caller with the tail pending on the context, and the next one walks its own front (scan, seam rounds, planes) on a stream
+ * of its own while it advances this tail whenever a host wait of that front returns (run_windowed). The states sit at the host
+ * read-backs the pass loop has always had: the run list's length, the chain kernel's "again", the staging sink's control words,
+ * the job table. A submission that is not deferred goes through the same states, waiting at each. */
+struct WindowedTail
 {
-   const auto entered = std::chrono::steady_clock::now(); /* (the stage log counts the host's tables from here) */
-   const uint32_t nJobs = (uint32_t)items.size();
-   const NfcConfig &cfg = ctx->configs[config];
+   enum State { RunList, Chain, Staging, Jobs };
+   State state = RunList;
+   bool deferred = false;          /* the submission has returned to its caller with this pending */
+   uint32_t config = 0, stride = 0;
+   std::vector<WindowedItem> items;
+   NfcScanArgs A;
+   NfcLaunch real, lanes;
+   const NfcConfig *dCfg = nullptr;
+   uint32_t *counters = nullptr;
+   const void *dJobs = nullptr;    /* the job table of the buffer set the submission's front wrote */
+   uint32_t nJobs = 0, nWindows = 0, windowBlocks = 0, firstWindowSlot = 0, finalLaneSlot = 0, pass = 0;
+   uint64_t totalSamples = 0;
+   ProfiledLaunch pw {nullptr, nullptr};
+   std::vector<hipEvent_t> passEvents; /* fork / join events in flight; back to the pool once the pass has been waited for */
+   bool sideRunning = false;       /* the side stream may be running kernels of the pass that the main stream does not wait for yet */
+   hipEvent_t ready = nullptr;     /* recorded behind the read-back the state waits for */
+   nfcgpu_ctx::StageSlot *slot = nullptr; /* staging slot of a host-resident submission: held until the tail is done */
+   bool debugStages = false;
+   std::chrono::steady_clock::time_point passBegan, stageBegan;
+};
 
-   /* A work buffer the device cannot give (NFCGPU_ENOMEM from grow()) is not the end of a submission as long as nothing of the
-    * streams has been touched - which holds up to the finish: the scan and the lanes only read the streams' state. The
-    * submission is then decoded a quarter of its length at a time (a quarter of every work buffer), and if that does not fit
-    * either by the sequential kernels, which need none. Any other error is the caller's. */
-   auto withoutTheMemory = [&](int code) -> int {
-      if (code != NFCGPU_ENOMEM)
-         return code;
+/* samples the pending tail's submission advances a slot's clock by (the host mirror follows when the tail completes) */
+uint32_t tail_ahead(const nfcgpu_ctx *ctx, uint32_t slot)
+{
+   if (!ctx->tail || ctx->tail->items.empty())
+      return 0u;
 
-      (void)hipGetLastError();
+   /* (a pending tail is a uniform submission's: a contiguous range of slots in order) */
+   const std::vector<WindowedItem> &items = ctx->tail->items;
+   const uint32_t first = items.front().slot;
 
-      uint32_t longest = 0;
-      for (const WindowedItem &it: items)
-         longest = it.count > longest ? it.count : longest;
+   if (slot >= first && slot - first < items.size() && items[slot - first].slot == slot)
+      return items[slot - first].count;
 
-      const uint32_t quarter = longest / 4u / NFC_SCAN_POINT * NFC_SCAN_POINT;
+   for (const WindowedItem &it: items)
+      if (it.slot == slot)
+         return it.count;
 
-      if (!ctx->inBlocks && quarter >= 65536u && quarter >= ctx->windowedMinSamples)
-         return run_in_blocks(ctx, config, items, stride, quarter);
+   return 0u;
+}
 
-      ctx->stats.fallback_streams += nJobs;
-      return launch_sequential(ctx, config, items, stride);
-   };
+/* one lane per slot: the carry lanes (and, at the end, the lanes that regenerate a job's final state) */
+int tail_decode_slots(nfcgpu_ctx *ctx, WindowedTail &T, bool carry, uint32_t firstSlot, uint32_t slotCount, hipStream_t on)
+{
+   if (slotCount == 0)
+      return NFCGPU_OK;
 
-   NfcScanParams sp;
+   NfcLaunch L = T.lanes;
+   L.firstSlot = firstSlot;
+   L.slotCount = slotCount;
+   L.firstBlock = firstSlot / NFC_LANES;
+   L.warmFront = carry ? 0u : NFC_WINDOW_WARM_FRONT;
+   L.warmCorr = carry ? 0u : NFC_WINDOW_WARM_CORR;
+
+   ProfiledLaunch wl {nullptr, nullptr};
+   record_span(ctx, ctx->timedWave, wl, true, on);
+   hipLaunchKernelGGL(NFC_BY_LAYOUT(T.A.stride, nfc_wave_kernel), dim3(slotCount), dim3(NFC_LANES), 0, on, T.dCfg, L, T.A, carry ? 0u : 2u); /* a wave per lane */
+   record_span(ctx, ctx->timedWave, wl, false, on);
+   HIP_TRY(ctx, hipGetLastError());
+   ctx->stats.launches++;
+   return NFCGPU_OK;
+}
+
+/* the speculative windows on the run list: persistent waves */
+int tail_decode_windows(nfcgpu_ctx *ctx, WindowedTail &T, uint32_t runLanes)
+{
+   NfcLaunch L = T.lanes;
+   L.warmFront = NFC_WINDOW_WARM_FRONT;
+   L.warmCorr = NFC_WINDOW_WARM_CORR;
+
+   ProfiledLaunch wl {nullptr, nullptr};
+   record_span(ctx, ctx->timedWave, wl, true);
+   hipLaunchKernelGGL(NFC_BY_LAYOUT(T.A.stride, nfc_wave_kernel), dim3(runLanes), dim3(NFC_LANES), 0, ctx->stream, T.dCfg, L, T.A, 1u); /* a wave per run-list entry */
+   record_span(ctx, ctx->timedWave, wl, false);
+   HIP_TRY(ctx, hipGetLastError());
+   ctx->stats.launches++;
+   return NFCGPU_OK;
+}
+
+/* the run list of the coming pass, and its length on the way to the host */
+int tail_list(nfcgpu_ctx *ctx, WindowedTail &T)
+{
+   const NfcScanArgs &A = T.A;
+   const NfcLaunch &lanes = T.lanes;
+   uint32_t *counters = T.counters;
+   const uint32_t pass = T.pass, windowBlocks = T.windowBlocks;
+   const NfcConfig *dCfg = T.dCfg;
+
+   T.passBegan = std::chrono::steady_clock::now();
+
+   if (T.nWindows)
    {
-      float corr = 3.0e38f;
-      if (cfg.enabled & 1u) corr = cfg.corrThreshold[0] < corr ? cfg.corrThreshold[0] : corr;
-      if (cfg.enabled & 4u) corr = cfg.corrThreshold[2] < corr ? cfg.corrThreshold[2] : corr;
-      if (cfg.enabled & 8u) corr = cfg.corrThreshold[3] < corr ? cfg.corrThreshold[3] : corr;
-      sp.rangeK = corr < 1.0e30f ? 0.49f * corr : 3.0e38f;
-      sp.edgeK = (cfg.enabled & 2u) ? 0.99f * cfg.minDepth[1] : 3.0e38f;
-      float deep = 1.0f;
-      for (int t = 0; t < 4; t++)
-         if ((cfg.enabled >> t) & 1u)
-            deep = cfg.maxDepth[t] < deep ? cfg.maxDepth[t] : deep;
-      sp.deepK = 0.98f * deep;
-      sp.chunkSamples = ctx->scanChunk;
-      sp.warmSamples = ctx->scanWarm;
-      sp.soloSamples = ctx->soloSamples;
-      sp.offGridAlone = 1u;
-
-      /* Every chunk pays the warm-up again, so chunks should be as long as the machine allows: one lane per chunk, and
-       * 131072 lanes (256 CUs x 4 SIMDs x 2 waves of the scan kernel's 204 registers x 64) are resident at a time.
-       * Measured on 4096 streams x 2^20 idle samples: 8192 -> 1347, 16384 -> 1673, 32768 -> 1906 GB/s. */
-      if (!ctx->scanChunkFixed)
+      HIP_TRY(ctx, hipMemsetAsync(counters + 2, 0, 8, ctx->stream)); /* run list: count and next */
+      if (!ctx->longFirst)
       {
-         uint64_t total = 0;
-         for (const WindowedItem &it: items)
-            total += it.count;
+         hipLaunchKernelGGL(nfc_window_lanes_kernel, dim3(windowBlocks), dim3(NFC_LANES), 0, ctx->stream, dCfg, A, lanes, pass, 0u, 0u, 0xFFFFFFFFu);
+         HIP_TRY(ctx, hipGetLastError());
+      }
+      else
+      {
+         /* longest lanes first: classes of 65536 samples and more, then halving down to NFCGPU_LONG_FIRST, then the rest */
+         uint32_t hi = 0xFFFFFFFFu, lo = 65536u > ctx->longFirst ? 65536u : ctx->longFirst;
 
-         /* (round 4: a sixteenth of that is enough lanes. What a submission of 2^29 samples - 512 busy streams, an eighth of
-          * config 5 - pays for are the rounds of second walks, a launch and a trip to the host each, and a chain of chunks that
-          * inherit a wrong envelope from each other is as many rounds as it has chunks: 27 rounds of 4096-sample chunks, 8 of
-          * 32768. 512 / 1024 dense streams x 2^20: 352 -> 321 ms per step.) */
-         uint64_t chunk = total / ctx->scanLanes / NFC_SCAN_POINT * NFC_SCAN_POINT;
-         if (chunk > 32768u)
-            chunk = 32768u;
-         if (chunk > sp.chunkSamples)
-            sp.chunkSamples = (uint32_t)chunk;
-
-         /* A small submission is one a caller waits for (a capture, a receiver's block): what counts is the time of the
-          * longest walk, chunk + warm-up at ~0.4 us per sample and lane. Shorter chunks and a warm-up that just covers the
-          * slowest recurrence (the average: 0.995^k) cut it; seams that do not verify cost a short second walk now. */
-         if (total <= (4u << 20))
+         for (uint32_t order = 1u;; order = 2u)
          {
-            if (sp.chunkSamples > 4096u)
-               sp.chunkSamples = 4096u;
-            if (sp.warmSamples > 3072u)
-               sp.warmSamples = 3072u;
+            hipLaunchKernelGGL(nfc_window_lanes_kernel, dim3(windowBlocks), dim3(NFC_LANES), 0, ctx->stream, dCfg, A, lanes, pass, order, lo, hi);
+            HIP_TRY(ctx, hipGetLastError());
+
+            if (lo == 0u)
+               break;
+
+            hi = lo;
+            lo = lo / 2u >= ctx->longFirst ? lo / 2u : 0u;
          }
       }
+      /* how many lanes the list holds: the later passes of a submission list a few thousand, then a few dozen, of its windows -
+       * the launch gets a grid of the list's length, not of the submission's window count */
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->tailHost + 1, counters + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
    }
 
-   /* job and chunk tables */
-   std::vector<NfcScanJob> jobs(nJobs);
-   std::vector<NfcScanChunk> chunks;
-   uint32_t tiles = 0, points = 0, tilesMost = 0;
-   uint64_t totalSamples = 0;
+   HIP_TRY(ctx, hipEventRecord(T.ready, ctx->stream));
+   T.state = WindowedTail::RunList;
+   return NFCGPU_OK;
+}
 
-   for (uint32_t j = 0; j < nJobs; j++)
+/* has the read-back the tail waits for arrived? (`block`: wait for it) */
+int tail_is_ready(nfcgpu_ctx *ctx, WindowedTail &T, bool block, bool *is)
+{
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+   /* (the emulated runtime's streams are synchronous: it has arrived) */
+   (void)block;
+   HIP_TRY(ctx, hipEventSynchronize(T.ready));
+   *is = true;
+#else
+   if (block)
    {
-      NfcScanJob &job = jobs[j];
-      std::memset(&job, 0, sizeof(job));
-      job.data = items[j].data;
-      job.count = items[j].count;
-      job.slot = items[j].slot;
-      job.firstChunk = (uint32_t)chunks.size();
-      job.chunks = (job.count + sp.chunkSamples - 1) / sp.chunkSamples;
-      job.firstTile = tiles;
-      job.firstPoint = points;
-      tiles += (job.count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE;
-      tilesMost = std::max(tilesMost, (job.count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE);
-      points += job.count / NFC_SCAN_POINT + 1;
-      totalSamples += job.count;
-
-      for (uint32_t k = 0; k < job.chunks; k++)
-         chunks.push_back(NfcScanChunk {j, k});
+      HIP_TRY(ctx, hipEventSynchronize(T.ready));
+      *is = true;
    }
-
-   /* Lanes inside busy signal: NFC_WINDOW_CUT samples apart when the submission is small (every lane is parallelism),
-    * further apart - fewer warm-ups, fewer hand-overs to go wrong - when that still leaves several lanes per wave slot
-    * of the machine (NFCGPU_LANES_WANTED, default 16384 = 8 per slot of 256 CUs x 8 waves) */
+   else
    {
-      uint64_t cut = ctx->lanesWanted ? totalSamples / ctx->lanesWanted : 0u;
-      cut = cut / NFC_SCAN_POINT * NFC_SCAN_POINT;
-      cut = cut < NFC_WINDOW_CUT ? NFC_WINDOW_CUT : (cut > ctx->cutMax ? ctx->cutMax : cut);
-
-      for (NfcScanJob &job: jobs)
-         job.cut = (uint32_t)cut;
+      const hipError_t q = hipEventQuery(T.ready);
+      if (q != hipSuccess && q != hipErrorNotReady)
+         return fail(ctx, NFCGPU_EHIP, "hipEventQuery(T.ready)", q);
+      *is = q == hipSuccess;
    }
+#endif
+   return NFCGPU_OK;
+}
 
-   const uint32_t nChunks = (uint32_t)chunks.size();
-   const uint32_t finalLaneSlot = (nJobs + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
-   const uint32_t firstWindowSlot = 2 * finalLaneSlot;
-
+/* one state of the tail, if what it waits for is there */
+int tail_step(nfcgpu_ctx *ctx, WindowedTail &T, bool block, bool *done)
+{
+   NfcScanArgs &A = T.A;
+   NfcLaunch &lanes = T.lanes;
+   NfcLaunch &real = T.real;
+   uint32_t *counters = T.counters;
+   const uint32_t nJobs = T.nJobs, nWindows = T.nWindows, firstWindowSlot = T.firstWindowSlot, finalLaneSlot = T.finalLaneSlot;
+   const uint64_t totalSamples = T.totalSamples;
+   const NfcConfig *dCfg = T.dCfg;
+   const std::vector<WindowedItem> &items = T.items;
+   std::vector<hipEvent_t> &passEvents = T.passEvents;
    int rc;
-   if ((rc = grow(ctx, ctx->wJobs, sizeof(NfcScanJob) * nJobs)) || (rc = grow(ctx, ctx->wChunks, sizeof(NfcScanChunk) * nChunks)) ||
-       (rc = grow(ctx, ctx->wPoints, sizeof(NfcScanPoint) * (size_t)points)) || (rc = grow(ctx, ctx->wSeams, sizeof(NfcScanSeam) * nChunks)) ||
-       (rc = grow(ctx, ctx->wChunkEdge, 4 * (size_t)nChunks)) || (rc = grow(ctx, ctx->wTiles, 4 * (size_t)tiles)) ||
-       (rc = grow(ctx, ctx->wTileStats, sizeof(NfcScanTile) * (size_t)tiles)) ||
-       (rc = grow(ctx, ctx->wCounters, 256)) || (rc = grow(ctx, ctx->wRepairs, sizeof(NfcScanChunk) * nChunks)) ||
-       (rc = grow(ctx, ctx->wRepairsEnv, sizeof(NfcScanChunk) * nChunks)))
-      return withoutTheMemory(rc);
 
-   /* lanes: a first guess (one window per 8192 samples); the window kernel reports what it needs */
-   uint32_t room = (uint32_t)(totalSamples / 8192) + 2 * nJobs + 64;
+   *done = false;
 
-   /* records per lane slot (carry lanes, final lanes, one per window); ring and frame-assembly storage per carry lane,
-    * final lane and per lane of the persistent waves that run the windows */
-   const size_t storageLanes = (size_t)firstWindowSlot; /* (a speculative window's rings live in LDS; one that runs to the end leaves a copy in the save area) */
-
-   auto growLanes = [&](uint32_t lanesWanted) -> int {
-      const size_t lanes = ((size_t)lanesWanted + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
-      int r;
-      if ((r = grow(ctx, ctx->wWindows, sizeof(NfcWindow) * lanes)) || (r = grow(ctx, ctx->wWorks, sizeof(NfcWork) * lanes)) ||
-          (r = grow(ctx, ctx->vStates, sizeof(NfcStreamState) * lanes)) || (r = grow(ctx, ctx->vCold, sizeof(NfcStreamCold) * lanes)) ||
-          (r = grow(ctx, ctx->wRunList, 4 * lanes)) ||
-          (r = grow(ctx, ctx->vRings, sizeof(float) * (size_t)kRingBlockFloats * (storageLanes / NFC_LANES))) ||
-          (r = grow(ctx, ctx->vBytes, (size_t)NFC_STREAM_BYTES * storageLanes)))
-         return r;
-      return NFCGPU_OK;
-   };
-
-   /* is there room already from an earlier, larger submission? */
    {
-      /* (every lane buffer has to hold them: one that could not be grown last time - NFCGPU_ENOMEM, the submission then taken in
-       * quarters - must not be asked for the room its neighbours got) */
-      size_t have = ctx->wWindows.bytes / sizeof(NfcWindow);
-      have = std::min(have, ctx->wWorks.bytes / sizeof(NfcWork));
-      have = std::min(have, ctx->vStates.bytes / sizeof(NfcStreamState));
-      have = std::min(have, ctx->vCold.bytes / sizeof(NfcStreamCold));
-      have = std::min(have, ctx->wRunList.bytes / 4);
-      if (have > (size_t)firstWindowSlot + room)
-         room = (uint32_t)(have - firstWindowSlot - NFC_LANES);
+      bool is = false;
+      if ((rc = tail_is_ready(ctx, T, block, &is)))
+         return rc;
+      if (!is)
+         return NFCGPU_OK;
    }
 
-   if ((rc = growLanes(firstWindowSlot + room)))
-      return withoutTheMemory(rc);
-
-   /* staging sink for the lanes' chained frame records (lanes that turn out not to be live write theirs too): room
-    * for four times the frame sink, at least 64 MiB; what does not fit is reported as dropped like any overflow */
-   {
-      size_t staging = (size_t)ctx->ownSinkWords * 16;
-      if (staging < (64u << 20))
-         staging = 64u << 20;
-      if (staging > 0xFFFFFFF0ull * 4ull)
-         staging = 0xFFFFFFF0ull * 4ull;
-      if ((rc = grow(ctx, ctx->vSink, staging)) || (rc = grow(ctx, ctx->vSinkCtl, 16)))
-         return withoutTheMemory(rc);
-   }
-
-   uint32_t *counters = (uint32_t *)ctx->wCounters.ptr;
-
-   HIP_TRY(ctx, hipMemcpyAsync(ctx->wJobs.ptr, jobs.data(), sizeof(NfcScanJob) * nJobs, hipMemcpyHostToDevice, ctx->stream));
-   HIP_TRY(ctx, hipMemcpyAsync(ctx->wChunks.ptr, chunks.data(), sizeof(NfcScanChunk) * nChunks, hipMemcpyHostToDevice, ctx->stream));
-   HIP_TRY(ctx, hipMemsetAsync(counters, 0, 256, ctx->stream));
-   HIP_TRY(ctx, hipMemsetAsync(ctx->vSinkCtl.ptr, 0, 16, ctx->stream));
-
-   NfcScanArgs A;
-   std::memset(&A, 0, sizeof(A));
-   A.jobs = (NfcScanJob *)ctx->wJobs.ptr;
-   A.nJobs = nJobs;
-   A.chunks = (const NfcScanChunk *)ctx->wChunks.ptr;
-   A.nChunks = nChunks;
-   A.stride = stride;
-   A.params = sp;
-   A.states = ctx->dStates;
-   A.points = (NfcScanPoint *)ctx->wPoints.ptr;
-   A.seams = (NfcScanSeam *)ctx->wSeams.ptr;
-   A.chunkEdge = (uint32_t *)ctx->wChunkEdge.ptr;
-   A.tiles = (uint32_t *)ctx->wTiles.ptr;
-   A.tileStats = (NfcScanTile *)ctx->wTileStats.ptr;
-   A.windows = (NfcWindow *)ctx->wWindows.ptr;
-   A.works = (NfcWork *)ctx->wWorks.ptr;
-   A.finalLaneSlot = finalLaneSlot;
-   A.firstWindowSlot = firstWindowSlot;
-   A.windowRoom = room;
-   A.windowCount = counters;
-   A.rerunCount = counters + 1;
-   A.runCount = counters + 2;
-   A.runNext = counters + 3;
-   A.runList = (uint32_t *)ctx->wRunList.ptr;
-   A.repairs = (NfcScanChunk *)ctx->wRepairs.ptr;
-   A.repairCount = counters + 7;
-   A.repairsEnv = ctx->envelopeMax ? (NfcScanChunk *)ctx->wRepairsEnv.ptr : nullptr; /* (NFCGPU_ENVELOPE_KERNEL=0: one list, one kernel) */
-   A.repairEnvCount = counters + 9;
-
-   /* save area for lanes that run to the end of the submission (nfc_scan_launch.h): a few per stream */
-   {
-      const uint32_t saveRoom = 2 * nJobs + 1024;
-      if ((rc = grow(ctx, ctx->vSaveRings, sizeof(float) * (size_t)(kRingBlockFloats / NFC_LANES) * saveRoom)) ||
-          (rc = grow(ctx, ctx->vSaveBytes, (size_t)NFC_STREAM_BYTES * saveRoom)))
-         return withoutTheMemory(rc);
-
-      A.saveRings = (float *)ctx->vSaveRings.ptr;
-      A.saveBytes = (uint8_t *)ctx->vSaveBytes.ptr;
-      A.saveNext = counters + 8;
-      A.saveRoom = saveRoom;
-   }
-
-   const NfcConfig *dCfg = ctx->dConfigs + config;
-
-   /* NFCGPU_WINDOW_DEBUG: where the time of a submission goes (synchronises at every mark) */
-   const bool debugStages = std::getenv("NFCGPU_WINDOW_DEBUG") != nullptr;
-   auto stageBegan = entered;
+   const bool debugStages = T.debugStages;
    auto mark = [&](const char *what) {
       if (!debugStages)
          return;
       (void)hipStreamSynchronize(ctx->stream);
       const auto now = std::chrono::steady_clock::now();
-      std::fprintf(stderr, "[nfcgpu] windowed stage %-10s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - stageBegan).count());
-      stageBegan = now;
+      std::fprintf(stderr, "[nfcgpu] windowed stage %-10s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - T.stageBegan).count());
+      T.stageBegan = now;
    };
 
-   mark("tables");
-
-   /* scan */
-   ProfiledLaunch pl {nullptr, nullptr};
-   record_span(ctx, ctx->timedScan, pl, true);
-   hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_scan_kernel), dim3((nChunks + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, A);
-   HIP_TRY(ctx, hipGetLastError());
-   record_span(ctx, ctx->timedScan, pl, false);
-   ctx->stats.scan_samples += totalSamples;
-
-   /* windows (again with more room when the guess was short) */
-   uint32_t nWindows = 0;
-
-   mark("scan");
-
-   /* (a grid has at most 65535 blocks in y: beyond 2^24 tiles in one job the kernel strides) */
-   const uint32_t tilesGridY = (tilesMost + 255) / 256 > 65535u ? 65535u : (tilesMost + 255) / 256;
-
-   /* a first run of the tile tests: how busy is each stream? Only a small submission is routed by that (below: `small`); a large
-    * one gets its tile flags once, when the envelopes they are formed from are the true ones (3.8 ms for the 67 M tiles of config 5) */
-   if (nJobs < NFC_LANES && !ctx->inBlocks)
+   switch (T.state)
    {
-      hipLaunchKernelGGL(nfc_tiles_kernel, dim3(nJobs, tilesGridY), dim3(256), 0, ctx->stream, dCfg, A, tilesMost);
-      HIP_TRY(ctx, hipGetLastError());
-   }
-
-   /* The front-end planes (below) are a walk of every chunk from its verified start state: 69 GB of stores for config 5, 32 ms
-    * of a device that the rounds of second walks after the first leave nearly idle (a few thousand chunks each, as long as
-    * their longest chain). Round 5: for a large submission that walk is started on a stream of its own (lowest priority) as soon as the first round's
-    * second walks are queued - by then nine chunks in ten start from their true state -, the seam check and the envelope
-    * walks note every start state they rewrite from then on (NfcScanArgs::planesStale), and those chunks' planes are written
-    * again when the rounds are over. */
-   const bool planesBeside = ctx->planesBeside && ctx->low != nullptr && totalSamples > (4u << 20);
-   bool planesStarted = false;
-
-   struct PlanesGuard
+   case WindowedTail::RunList:
    {
-      nfcgpu_ctx *ctx;
-      bool running;
-      ~PlanesGuard()
-      {
-         if (running)
-            (void)hipStreamSynchronize(ctx->low); /* (whatever way the function is left: nobody reuses what the walk reads or writes while it runs) */
-      }
-   } planesGuard {ctx, false};
-
-   if (planesBeside)
-   {
-      if ((rc = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) || (rc = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * nChunks)) ||
-          (rc = grow(ctx, ctx->wPlanesStale, 4u * (size_t)nChunks)))
-         return withoutTheMemory(rc);
-
-      HIP_TRY(ctx, hipMemsetAsync(ctx->wPlanesStale.ptr, 0, 4u * (size_t)nChunks, ctx->stream));
-   }
-
-   /* seams: chunks that did not start from the true state are walked again, a round at a time */
-
-   for (uint32_t round = 0;; round++)
-   {
-      if (debugStages && std::atoi(std::getenv("NFCGPU_WINDOW_DEBUG")) >= 4)
-      {
-         /* which fields keep seams from verifying (host-side look at the records the seam check is about to judge) */
-         std::vector<NfcScanSeam> sm(nChunks);
-         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-         HIP_TRY(ctx, hipMemcpy(sm.data(), ctx->wSeams.ptr, sizeof(NfcScanSeam) * nChunks, hipMemcpyDeviceToHost));
-         uint32_t n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-         for (uint32_t j = 0; j < nJobs; j++)
-            for (uint32_t k = 1; k < jobs[j].chunks; k++)
-            {
-               const NfcScanPoint &a = sm[jobs[j].firstChunk + k].start, &b = sm[jobs[j].firstChunk + k - 1].end;
-               const bool env = std::memcmp(&a.env, &b.env, 4) != 0 || a.pulseFilter != b.pulseFilter;
-               const bool n1 = std::memcmp(&a.n1, &b.n1, 4) != 0, mdev = std::memcmp(&a.mdev, &b.mdev, 4) != 0, avg = std::memcmp(&a.avg, &b.avg, 4) != 0;
-               const bool peak = std::memcmp(&a.edgePeak, &b.edgePeak, 4) != 0, zone = ((a.zone ^ b.zone) & 0xFFu) != 0;
-               const bool time = (a.zone & 0x100u) && (b.zone & 0x100u) && a.edgeTime != b.edgeTime;
-               n[0] += env; n[1] += n1; n[2] += mdev; n[3] += avg; n[4] += peak; n[5] += zone; n[6] += time;
-               n[7] += (n1 || mdev || avg || peak || zone) ? 1u : 0u;
-            }
-         std::fprintf(stderr, "[nfcgpu]    before round %u, seams that differ in: envelope / counter %u, n1 %u, deviation %u, average %u, edge peak %u, zone %u, known edge times %u; in anything but the envelope %u\n",
-                      round, n[0], n[1], n[2], n[3], n[4], n[5], n[6], n[7]);
-      }
-
-      HIP_TRY(ctx, hipMemsetAsync(counters + 7, 0, 4, ctx->stream));
-      HIP_TRY(ctx, hipMemsetAsync(counters + 9, 0, 4, ctx->stream));
-      hipLaunchKernelGGL(nfc_seams_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, A, round == 0 ? 1u : 0u);
-      HIP_TRY(ctx, hipGetLastError());
-
-      /* chunks to walk again: every recurrence of them (A.repairs), the envelope tracker alone (A.repairsEnv: listed apart by
-       * the seam check when the envelope kernel is on) */
-      uint32_t word[3] = {0, 0, 0};
-      HIP_TRY(ctx, hipMemcpyAsync(word, counters + 7, 12, hipMemcpyDeviceToHost, ctx->stream));
-
-      /* (a small submission: how busy are its streams? the tile tests have counted) */
-      const bool small = round == 0 && nJobs < NFC_LANES && !ctx->inBlocks;
-      if (small)
-         HIP_TRY(ctx, hipMemcpyAsync(jobs.data(), ctx->wJobs.ptr, sizeof(NfcScanJob) * nJobs, hipMemcpyDeviceToHost, ctx->stream));
-
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      const uint32_t whole = word[0], alone = word[2];
-      const uint32_t repairs = whole + alone;
-
-      /* A few long busy streams: the passes the chain needs grow with the length of the submission (a frame that changes
-       * the protocol timing is learnt one generation per pass), so it is decoded in blocks, each settled before the next.
-       * Nothing has been touched yet (the scan only reads). */
-      if (small)
-      {
-         uint32_t longest = 0;
-         bool busy = false;
-
-         for (uint32_t j = 0; j < nJobs; j++)
-         {
-            const uint64_t nTiles = ((uint64_t)jobs[j].count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE;
-            busy = busy || (uint64_t)jobs[j].busyTiles * 100u > nTiles * ctx->busyPercent;
-            longest = jobs[j].count > longest ? jobs[j].count : longest;
-         }
-
-         if (busy && longest > ctx->blockSamples)
-            return run_in_blocks(ctx, config, items, stride);
-      }
-
-      if (debugStages)
-         std::fprintf(stderr, "[nfcgpu]    seams round %u: %u chunks to walk again\n", round, repairs);
-
-      if (!repairs)
-         break;
-
-      /* The chunks whose envelope tracker alone started wrong - from the second round on that is all of them: chains of chunks
-       * that inherit a wrong envelope from each other, a chunk per round - go to a kernel that does nothing else, a wavefront
-       * per chunk (nfc_envelope.hpp): a round then costs the tracker's own latency over one chunk instead of the scan kernel's
-       * row machinery over it (9 ms of 32768 samples, however short the list). A list too long for a wave a chunk to pay (the
-       * first round of a large submission: a quarter of its chunks, the scan kernel's 64 chunks per wave are the better use
-       * of the machine) stays with the scan kernel's envelope-only branch (NFCGPU_ENVELOPE_KERNEL: the longest list the
-       * envelope kernel is given). */
-      if (debugStages && alone && alone <= ctx->envelopeMax)
-         std::fprintf(stderr, "[nfcgpu]    ... %u of them the envelope tracker's alone, by the envelope kernel\n", alone);
-
-      ProfiledLaunch pr {nullptr, nullptr};
-      record_span(ctx, ctx->timedScan, pr, true);
-
-      const bool byWaves = alone && alone <= ctx->envelopeMax;
-
-      if (whole || (alone && !byWaves))
-      {
-         /* the scan kernel: the chunks walked whole, and a list of envelope-only ones too long for a wave each, in one launch */
-         NfcScanArgs R = A;
-         R.chunks = A.repairs;
-         R.nChunks = whole;
-         R.chunksMore = byWaves ? nullptr : A.repairsEnv;
-         R.nChunksMore = byWaves ? 0u : alone;
-
-         const uint32_t listedNow = R.nChunks + R.nChunksMore;
-
-         hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_scan_kernel), dim3((listedNow + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, R);
-         HIP_TRY(ctx, hipGetLastError());
-      }
-
-      if (byWaves)
-      {
-         NfcScanArgs R = A;
-         R.chunks = A.repairsEnv;
-         R.nChunks = alone;
-         R.followChains = alone <= ctx->envelopeFollowMax ? 1u : 0u;
-
-         hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_envelope_kernel), dim3(alone), dim3(NFC_LANES), 0, ctx->stream, dCfg, R);
-         HIP_TRY(ctx, hipGetLastError());
-      }
-
-      record_span(ctx, ctx->timedScan, pr, false);
-      ctx->stats.scan_repairs += repairs;
-
-      if (planesBeside && round == 0)
-      {
-         /* the planes of every chunk, beside the rounds to come */
-         HIP_TRY(ctx, hipEventRecord(ctx->forkEvent, ctx->stream));
-         HIP_TRY(ctx, hipStreamWaitEvent(ctx->low, ctx->forkEvent, 0));
-         planesGuard.running = true;
-
-         NfcScanArgs P = A;
-         P.planes = (float *)ctx->wPlanes.ptr;
-         P.chunks = (const NfcScanChunk *)ctx->wChunks.ptr; /* (the submission's chunk table as it is: the walk takes no notice of the repair marks) */
-         P.nChunks = nChunks;
-         /* a lane per piece, and the pieces of a chunk have to tile it: the largest multiple of the distance of the stored
-          * points (every lane starts from one) that is no longer than NFCGPU_PLANES_BESIDE_PIECE and divides the chunk. (Until
-          * round 6 the quotient was truncated: with a chunk that is no multiple of the piece - the default sizing gives any
-          * multiple of 512 for totals between 2^28 and 2^30 samples - the tail of every chunk that was not walked again got no
-          * planes at all.) A chunk is a multiple of the points' distance, so that distance always does. */
-         P.planesPiece = ctx->planesBesidePiece / NFC_SCAN_POINT * NFC_SCAN_POINT;
-         if (P.planesPiece > sp.chunkSamples)
-            P.planesPiece = sp.chunkSamples / NFC_SCAN_POINT * NFC_SCAN_POINT;
-         while (P.planesPiece > NFC_SCAN_POINT && sp.chunkSamples % P.planesPiece != 0u)
-            P.planesPiece -= NFC_SCAN_POINT;
-         if (P.planesPiece && sp.chunkSamples % P.planesPiece != 0u)
-            P.planesPiece = 0u; /* (a chunk that is no multiple of the points' distance: a lane per chunk, from its start) */
-         P.planesPerChunk = P.planesPiece ? sp.chunkSamples / P.planesPiece : 0u;
-
-         const uint64_t lanesOfIt = (uint64_t)nChunks * (P.planesPerChunk ? P.planesPerChunk : 1u);
-
-         ProfiledLaunch pp {nullptr, nullptr};
-         record_span(ctx, ctx->timedPlanes, pp, true, ctx->low);
-         hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)((lanesOfIt + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->low, dCfg, P);
-         HIP_TRY(ctx, hipGetLastError());
-         record_span(ctx, ctx->timedPlanes, pp, false, ctx->low);
-         HIP_TRY(ctx, hipEventRecord(ctx->joinEvent, ctx->low));
-
-         planesStarted = true;
-         A.planesStale = (uint32_t *)ctx->wPlanesStale.ptr; /* from the next round on */
-      }
-   }
-   hipLaunchKernelGGL(nfc_tiles_kernel, dim3(nJobs, tilesGridY), dim3(256), 0, ctx->stream, dCfg, A, tilesMost);
-   HIP_TRY(ctx, hipGetLastError());
-
-   mark("seams");
-
-   /* The wave decoder takes the front end's results per sample instead of walking it again: a second walk of every
-    * chunk from its verified start state (the repair form of the scan: no warm-up) writes them. */
-   if (planesStarted)
-   {
-      /* the walk over all chunks has run beside the rounds: the chunks whose start state changed under it, again */
-      HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->joinEvent, 0));
-      planesGuard.running = false; /* (the main stream now waits for it) */
-
-      HIP_TRY(ctx, hipMemsetAsync(counters + 11, 0, 4, ctx->stream));
-      hipLaunchKernelGGL(nfc_planes_stale_kernel, dim3((nChunks + 255) / 256), dim3(256), 0, ctx->stream, A, (const NfcScanChunk *)ctx->wChunks.ptr, nChunks,
-                         (NfcScanChunk *)ctx->wPlaneChunks.ptr, counters + 11);
-      HIP_TRY(ctx, hipGetLastError());
-
-      uint32_t again = 0;
-      HIP_TRY(ctx, hipMemcpyAsync(&again, counters + 11, 4, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-
-      A.planes = (float *)ctx->wPlanes.ptr;
-      A.planesStale = nullptr;
-
-      if (debugStages)
-         std::fprintf(stderr, "[nfcgpu]    planes written beside the rounds; %u chunks of %u again\n", again, nChunks);
-
-      if (again)
-      {
-         NfcScanArgs P = A;
-         /* (a stored point per lane - 512 samples, from the points the rounds have left true -: a few thousand chunks a lane each
-          * would take as long as one chunk's walk, 12 ms, with the device all but idle) */
-         P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
-         P.nChunks = again;
-         P.planesPiece = NFC_SCAN_POINT;
-         P.planesPerChunk = sp.chunkSamples / NFC_SCAN_POINT;
-
-         ProfiledLaunch pp {nullptr, nullptr};
-         record_span(ctx, ctx->timedPlanes, pp, true);
-         hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)(((uint64_t)again * P.planesPerChunk + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->stream, dCfg, P);
-         HIP_TRY(ctx, hipGetLastError());
-         record_span(ctx, ctx->timedPlanes, pp, false);
-      }
-
-      mark("planes");
-   }
-   else
-   {
-      /* A small submission - one a caller waits for - is walked a lane per stored point instead of a lane per chunk: 512 samples
-       * instead of 4096 on the way of everything that follows (NFCGPU_PLANES_PIECE; a short capture: 1.1 -> 0.2 ms) */
-      const uint32_t piece = totalSamples <= (4u << 20) ? ctx->planesPiece / NFC_SCAN_POINT * NFC_SCAN_POINT : 0u;
-
-      std::vector<NfcScanChunk> all;
-
-      if (piece)
-      {
-         for (uint32_t j = 0; j < nJobs; j++)
-            for (uint32_t i = 0; i * piece < jobs[j].count; i++)
-               all.push_back(NfcScanChunk {j, i | NFC_CHUNK_REPAIR});
-      }
-      else
-      {
-         all = chunks;
-         for (NfcScanChunk &c: all)
-            c.index |= NFC_CHUNK_REPAIR;
-      }
-
-      const uint32_t nPlaneLanes = (uint32_t)all.size();
-
-      if ((rc = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) || (rc = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * all.size())))
-      {
-         /* (the planes are 16 bytes per sample of the submission: 64 GiB for 4096 streams x 2^20) */
-         return withoutTheMemory(rc);
-      }
-
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->wPlaneChunks.ptr, all.data(), sizeof(NfcScanChunk) * all.size(), hipMemcpyHostToDevice, ctx->stream));
-
-      A.planes = (float *)ctx->wPlanes.ptr;
-
-      NfcScanArgs P = A;
-      P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
-      P.nChunks = nPlaneLanes;
-      P.planesPiece = piece;
-
-      ProfiledLaunch pp {nullptr, nullptr};
-      record_span(ctx, ctx->timedPlanes, pp, true);
-      hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((nPlaneLanes + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, ctx->stream, dCfg, P);
-      HIP_TRY(ctx, hipGetLastError());
-      record_span(ctx, ctx->timedPlanes, pp, false);
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); /* (the chunk list is a local) */
-
-      mark("planes");
-   }
-
-   for (int attempt = 0; attempt < 2; attempt++)
-   {
-      hipLaunchKernelGGL(nfc_windows_kernel, dim3(nJobs), dim3(64), 0, ctx->stream, A);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipMemcpyAsync(&nWindows, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-
-      if (nWindows <= room)
-         break;
-
-      room = nWindows + NFC_LANES;
-      if ((rc = growLanes(firstWindowSlot + room)))
-         return withoutTheMemory(rc);
-
-      A.windows = (NfcWindow *)ctx->wWindows.ptr;
-      A.works = (NfcWork *)ctx->wWorks.ptr;
-         A.runList = (uint32_t *)ctx->wRunList.ptr;
-      A.windowRoom = room;
-      HIP_TRY(ctx, hipMemsetAsync(counters, 0, 4, ctx->stream));
-   }
-
-   mark("windows");
-
-   NfcLaunch real = base_launch(ctx);
-
-   NfcLaunch lanes;
-   std::memset(&lanes, 0, sizeof(lanes));
-   lanes.states = (NfcStreamState *)ctx->vStates.ptr;
-   lanes.cold = (NfcStreamCold *)ctx->vCold.ptr;
-   lanes.rings = (float *)ctx->vRings.ptr;
-   lanes.bytes = (uint8_t *)ctx->vBytes.ptr;
-   lanes.sink = (uint32_t *)ctx->vSink.ptr;
-   lanes.sinkCtl = (uint32_t *)ctx->vSinkCtl.ptr;
-   lanes.sinkWords = (uint32_t)(ctx->vSink.bytes / 4 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : ctx->vSink.bytes / 4);
-   if (ctx->stagingWords && lanes.sinkWords > ctx->stagingWords)
-      lanes.sinkWords = ctx->stagingWords; /* (NFCGPU_STAGING_WORDS: the tests make it run full) */
-   lanes.ringBlockFloats = kRingBlockFloats;
-   lanes.works = (const NfcWork *)ctx->wWorks.ptr;
-   lanes.windows = (NfcWindow *)ctx->wWindows.ptr;
-   lanes.jobs = (const NfcScanJob *)ctx->wJobs.ptr;
-   lanes.laneStats = counters + 4;
-   lanes.uniformStride = stride;
-
-   /* lanes */
-   hipLaunchKernelGGL(nfc_carry_lanes_kernel, dim3(nJobs), dim3(NFC_LANES), 0, ctx->stream, A, real, lanes, 0u);
-   HIP_TRY(ctx, hipGetLastError());
-
-   const uint32_t windowBlocks = (nWindows + NFC_LANES - 1) / NFC_LANES;
-
-   /* one lane per slot: the carry lanes (and, at the end, the lanes that regenerate a job's final state) */
-   auto decodeSlots = [&](bool carry, uint32_t firstSlot, uint32_t slotCount, hipStream_t on) -> int {
-      if (slotCount == 0)
-         return NFCGPU_OK;
-
-      NfcLaunch L = lanes;
-      L.firstSlot = firstSlot;
-      L.slotCount = slotCount;
-      L.firstBlock = firstSlot / NFC_LANES;
-      L.warmFront = carry ? 0u : NFC_WINDOW_WARM_FRONT;
-      L.warmCorr = carry ? 0u : NFC_WINDOW_WARM_CORR;
-
-      ProfiledLaunch wl {nullptr, nullptr};
-      record_span(ctx, ctx->timedWave, wl, true, on);
-      hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_wave_kernel), dim3(slotCount), dim3(NFC_LANES), 0, on, dCfg, L, A, carry ? 0u : 2u); /* a wave per lane */
-      record_span(ctx, ctx->timedWave, wl, false, on);
-      HIP_TRY(ctx, hipGetLastError());
-      ctx->stats.launches++;
-      return NFCGPU_OK;
-   };
-
-   /* the speculative windows on the run list: persistent waves */
-   auto decodeWindows = [&](uint32_t runLanes) -> int {
-      NfcLaunch L = lanes;
-      L.warmFront = NFC_WINDOW_WARM_FRONT;
-      L.warmCorr = NFC_WINDOW_WARM_CORR;
-
-      ProfiledLaunch wl {nullptr, nullptr};
-      record_span(ctx, ctx->timedWave, wl, true);
-      hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_wave_kernel), dim3(runLanes), dim3(NFC_LANES), 0, ctx->stream, dCfg, L, A, 1u); /* a wave per run-list entry */
-      record_span(ctx, ctx->timedWave, wl, false);
-      HIP_TRY(ctx, hipGetLastError());
-      ctx->stats.launches++;
-      return NFCGPU_OK;
-   };
-
-   ProfiledLaunch pw {nullptr, nullptr};
-   record_span(ctx, ctx->timedWindow, pw, true);
-
-   uint32_t pass = 0;
-   const bool debugPasses = std::getenv("NFCGPU_WINDOW_DEBUG") != nullptr;
-   std::vector<hipEvent_t> passEvents; /* fork / join events in flight; back to the pool once the pass has been waited for */
-
-   /* Whatever way this function is left while the side stream may still be running kernels of the pass (a launch that
-    * failed after the fork, an event that could not be recorded): the side stream is waited for before anyone reuses the
-    * staging slot or the lane buffers it reads, and the events of the pass go back to the pool. */
-   struct SideGuard
-   {
-      nfcgpu_ctx *ctx;
-      std::vector<hipEvent_t> *events;
-      bool running;
-      ~SideGuard()
-      {
-         if (running)
-            (void)hipStreamSynchronize(ctx->side);
-         for (hipEvent_t e: *events)
-            ctx->eventPool.push_back(e);
-         events->clear();
-      }
-   } sideGuard {ctx, &passEvents, false};
-
-   for (;;)
-   {
-      const auto passBegan = std::chrono::steady_clock::now();
-
-      if (nWindows)
-      {
-         HIP_TRY(ctx, hipMemsetAsync(counters + 2, 0, 8, ctx->stream)); /* run list: count and next */
-         if (!ctx->longFirst)
-         {
-            hipLaunchKernelGGL(nfc_window_lanes_kernel, dim3(windowBlocks), dim3(NFC_LANES), 0, ctx->stream, dCfg, A, lanes, pass, 0u, 0u, 0xFFFFFFFFu);
-            HIP_TRY(ctx, hipGetLastError());
-         }
-         else
-         {
-            /* longest lanes first: classes of 65536 samples and more, then halving down to NFCGPU_LONG_FIRST, then the rest */
-            uint32_t hi = 0xFFFFFFFFu, lo = 65536u > ctx->longFirst ? 65536u : ctx->longFirst;
-
-            for (uint32_t order = 1u;; order = 2u)
-            {
-               hipLaunchKernelGGL(nfc_window_lanes_kernel, dim3(windowBlocks), dim3(NFC_LANES), 0, ctx->stream, dCfg, A, lanes, pass, order, lo, hi);
-               HIP_TRY(ctx, hipGetLastError());
-
-               if (lo == 0u)
-                  break;
-
-               hi = lo;
-               lo = lo / 2u >= ctx->longFirst ? lo / 2u : 0u;
-            }
-         }
-      }
-
-      /* how many lanes the list holds: the later passes of a submission list a few thousand, then a few dozen, of its windows -
-       * the launch gets a grid of the list's length, not of the submission's window count */
-      uint32_t runLanes = 0;
-      if (nWindows)
-      {
-         HIP_TRY(ctx, hipMemcpyAsync(&runLanes, counters + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-         if (runLanes > nWindows)
-            runLanes = nWindows;
-      }
+      const uint32_t pass = T.pass;
+      uint32_t runLanes = nWindows ? ctx->tailHost[1] : 0u;
+      if (runLanes > nWindows)
+         runLanes = nWindows;
 
       /* the carry lanes (later passes: those the chain kernel sent on): from the stream's own state, which has not
        * been touched */
@@ -1508,9 +1243,9 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
       if (ctx->sideMode == 0 || nWindows == 0 || runLanes == 0)
       {
          /* nothing to run beside (or NFCGPU_SIDE_STREAM=0): one stream */
-         if ((rc = decodeSlots(true, 0, nJobs, ctx->stream)))
+         if ((rc = tail_decode_slots(ctx, T, true, 0, nJobs, ctx->stream)))
             return rc;
-         if (nWindows && runLanes && (rc = decodeWindows(runLanes)))
+         if (nWindows && runLanes && (rc = tail_decode_windows(ctx, T, runLanes)))
             return rc;
       }
       else
@@ -1527,27 +1262,35 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
          HIP_TRY(ctx, hipEventRecord(fork, ctx->stream));
          HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, fork, 0));
-         sideGuard.running = true;
+         T.sideRunning = true;
 
-         if ((rc = decodeSlots(true, 0, nJobs, ctx->side)))
+         if ((rc = tail_decode_slots(ctx, T, true, 0, nJobs, ctx->side)))
             return rc;
 
          HIP_TRY(ctx, hipEventRecord(join, ctx->side));
 
-         if (runLanes && (rc = decodeWindows(runLanes)))
+         if (runLanes && (rc = tail_decode_windows(ctx, T, runLanes)))
             return rc;
 
          HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, join, 0));
-         sideGuard.running = false; /* (the main stream now waits for it) */
+         T.sideRunning = false; /* (the main stream now waits for it) */
       }
 
       HIP_TRY(ctx, hipMemsetAsync(counters + 1, 0, 4, ctx->stream));
       hipLaunchKernelGGL(nfc_chain_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, A, lanes, nJobs >= NFC_LANES ? ctx->maxPasses : ctx->maxPassesFew);
       HIP_TRY(ctx, hipGetLastError());
 
-      uint32_t again = 0;
-      HIP_TRY(ctx, hipMemcpyAsync(&again, counters + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->tailHost, counters + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipEventRecord(T.ready, ctx->stream));
+      T.state = WindowedTail::Chain;
+      return NFCGPU_OK;
+   }
+
+   case WindowedTail::Chain:
+   {
+      const uint32_t pass = T.pass;
+      const uint32_t again = ctx->tailHost[0];
+      const auto passBegan = T.passBegan;
 
 #if defined(NFCGPU_TUNING_KNOBS) || defined(NFCGPU_EMULATED_TEST_BUILD)
       /* (the tuning build: NFCGPU_DUMP_WINDOWS=<file> - the pieces of the first pass as they ended, five words each: job, start,
@@ -1569,7 +1312,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
          }
 #endif
 
-      if (debugPasses)
+      if (debugStages)
       {
          uint32_t ls[3] = {0, 0, 0}, tilesTaken = 0;
          HIP_TRY(ctx, hipMemcpy(ls, counters + 4, 12, hipMemcpyDeviceToHost));
@@ -1701,119 +1444,1175 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
       passEvents.clear();
 
       ctx->stats.window_passes++;
-      pass++;
+      T.pass++;
 
-      if (!again || !nWindows)
-         break;
+      if (again && nWindows)
+         return tail_list(ctx, T);
+
+      mark("passes");
+
+      /* a library whose wave decoder was built with -DNFC_WAVE_VERIFY (Makefile: libnfcgpu_verify.so) has decoded every tile twice
+       * and counted (csrc/nfc_wave.hip); a product build leaves the words at zero */
+      if (std::getenv("NFCGPU_WAVE_VERIFY_REPORT"))
+      {
+         uint32_t v[4] = {0, 0, 0, 0};
+         HIP_TRY(ctx, hipMemcpyAsync(v, counters + 12, 16, hipMemcpyDeviceToHost, ctx->stream));
+         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+         std::fprintf(stderr, "[nfcgpu] wave verify: %u tiles decoded twice (bulk paths / step machine alone), %u differ", v[0], v[1]);
+         if (v[1])
+            std::fprintf(stderr, " (the first at stream position %u of lane slot %u)", v[2], v[3]);
+         std::fprintf(stderr, "\n");
+      }
+
+      /* The lanes chain their frame records in a staging sink that is sized from an estimate and written by every lane of
+       * every pass, live in the end or not. Should it have run full, frames of live lanes may be among the ones that did not
+       * fit: nothing of the streams has been touched yet, so the submission is decoded by the sequential kernels instead. */
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->tailHost + 2, ctx->vSinkCtl.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipEventRecord(T.ready, ctx->stream));
+      T.state = WindowedTail::Staging;
+      return NFCGPU_OK;
    }
 
-   mark("passes");
-
-   /* a library whose wave decoder was built with -DNFC_WAVE_VERIFY (Makefile: libnfcgpu_verify.so) has decoded every tile twice
-    * and counted (csrc/nfc_wave.hip); a product build leaves the words at zero */
-   if (std::getenv("NFCGPU_WAVE_VERIFY_REPORT"))
+   case WindowedTail::Staging:
    {
-      uint32_t v[4] = {0, 0, 0, 0};
-      HIP_TRY(ctx, hipMemcpyAsync(v, counters + 12, 16, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      std::fprintf(stderr, "[nfcgpu] wave verify: %u tiles decoded twice (bulk paths / step machine alone), %u differ", v[0], v[1]);
-      if (v[1])
-         std::fprintf(stderr, " (the first at stream position %u of lane slot %u)", v[2], v[3]);
-      std::fprintf(stderr, "\n");
-   }
-
-   /* The lanes chain their frame records in a staging sink that is sized from an estimate and written by every lane of
-    * every pass, live in the end or not. Should it have run full, frames of live lanes may be among the ones that did not
-    * fit: nothing of the streams has been touched yet, so the submission is decoded by the sequential kernels instead. */
-   {
-      uint32_t stagingCtl[2] = {0, 0};
-      HIP_TRY(ctx, hipMemcpyAsync(stagingCtl, ctx->vSinkCtl.ptr, 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-
-      if (stagingCtl[1])
+      if (ctx->tailHost[3])
       {
          HIP_TRY(ctx, hipMemsetAsync(ctx->vSinkCtl.ptr, 0, 16, ctx->stream));
          ctx->stats.fallback_streams += nJobs;
-         return launch_sequential(ctx, config, items, stride);
+         *done = true;
+         return launch_sequential(ctx, T.config, items, T.stride);
       }
+
+      /* the state a stream is left in: its last lane's, run once more with storage of its own */
+      hipLaunchKernelGGL(nfc_final_lanes_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, dCfg, A, lanes);
+      HIP_TRY(ctx, hipGetLastError());
+
+      if ((rc = tail_decode_slots(ctx, T, false, finalLaneSlot, nJobs, ctx->stream)))
+         return rc;
+
+      record_span(ctx, ctx->timedWindow, T.pw, false);
+
+      hipLaunchKernelGGL(nfc_finish_kernel, dim3(nJobs), dim3(NFC_LANES), 0, ctx->stream, A, real, lanes);
+      HIP_TRY(ctx, hipGetLastError());
+
+      /* (the job table comes back into pinned memory: a copy into pageable memory would hold the host until it is done) */
+      if (ctx->tailJobsBytes < sizeof(NfcScanJob) * nJobs)
+      {
+         if (ctx->tailJobs)
+            (void)hipHostFree(ctx->tailJobs);
+         ctx->tailJobs = nullptr;
+         ctx->tailJobsBytes = 0;
+         if (hipHostMalloc((void **)&ctx->tailJobs, sizeof(NfcScanJob) * nJobs, hipHostMallocDefault) != hipSuccess)
+         {
+            (void)hipGetLastError();
+            ctx->tailJobs = nullptr;
+            return fail(ctx, NFCGPU_ENOMEM, "pinned buffer for the job table of the time-parallel path could not be allocated");
+         }
+         ctx->tailJobsBytes = sizeof(NfcScanJob) * nJobs;
+      }
+
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->tailJobs, T.dJobs, sizeof(NfcScanJob) * nJobs, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipEventRecord(T.ready, ctx->stream));
+      T.state = WindowedTail::Jobs;
+      return NFCGPU_OK;
    }
 
-   /* the state a stream is left in: its last lane's, run once more with storage of its own */
-   hipLaunchKernelGGL(nfc_final_lanes_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, dCfg, A, lanes);
-   HIP_TRY(ctx, hipGetLastError());
-
-   if ((rc = decodeSlots(false, finalLaneSlot, nJobs, ctx->stream)))
-      return rc;
-
-   record_span(ctx, ctx->timedWindow, pw, false);
-
-   hipLaunchKernelGGL(nfc_finish_kernel, dim3(nJobs), dim3(NFC_LANES), 0, ctx->stream, A, real, lanes);
-   HIP_TRY(ctx, hipGetLastError());
-
-   HIP_TRY(ctx, hipMemcpyAsync(jobs.data(), ctx->wJobs.ptr, sizeof(NfcScanJob) * nJobs, hipMemcpyDeviceToHost, ctx->stream));
-   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-
-   mark("finish");
-
-   if (debugStages && std::atoi(std::getenv("NFCGPU_WINDOW_DEBUG")) >= 3 && nWindows)
+   case WindowedTail::Jobs:
    {
-      /* how much of what the speculative lanes decoded ended up in the stream (the rest was overrun by a lane that could
-       * not hand over, or decoded again in a later pass) */
-      std::vector<NfcWindow> ws(nWindows);
-      HIP_TRY(ctx, hipMemcpy(ws.data(), (const NfcWindow *)ctx->wWindows.ptr + firstWindowSlot, sizeof(NfcWindow) * ws.size(), hipMemcpyDeviceToHost));
-      uint64_t all = 0, live = 0, liveLanes = 0;
-      for (const NfcWindow &w: ws)
+      const NfcScanJob *jobs = ctx->tailJobs;
+
+      mark("finish");
+
+      if (debugStages && std::atoi(std::getenv("NFCGPU_WINDOW_DEBUG")) >= 3 && nWindows)
       {
-         all += w.stop - w.start;
-         if (w.live)
+         /* how much of what the speculative lanes decoded ended up in the stream (the rest was overrun by a lane that could
+          * not hand over, or decoded again in a later pass) */
+         std::vector<NfcWindow> ws(nWindows);
+         HIP_TRY(ctx, hipMemcpy(ws.data(), (const NfcWindow *)ctx->wWindows.ptr + firstWindowSlot, sizeof(NfcWindow) * ws.size(), hipMemcpyDeviceToHost));
+         uint64_t all = 0, live = 0, liveLanes = 0;
+         for (const NfcWindow &w: ws)
          {
-            live += w.stop - w.start;
-            liveLanes++;
+            all += w.stop - w.start;
+            if (w.live)
+            {
+               live += w.stop - w.start;
+               liveLanes++;
+            }
+         }
+         std::fprintf(stderr, "[nfcgpu] speculative lanes: %zu, %llu samples as they last ran; live in the end: %llu lanes, %llu samples (%.1f %%); submission: %llu samples\n", ws.size(),
+                      (unsigned long long)all, (unsigned long long)liveLanes, (unsigned long long)live, all ? 100.0 * (double)live / (double)all : 0.0, (unsigned long long)totalSamples);
+      }
+
+      ctx->stats.windows += nWindows + nJobs;
+      ctx->stats.samples += totalSamples;
+      ctx->dirty = true;
+
+      std::vector<WindowedItem> fallback;
+
+      for (uint32_t j = 0; j < nJobs; j++)
+      {
+         if (jobs[j].status & NFC_JOB_INVALID)
+            fallback.push_back(items[j]);
+         else
+         {
+            ctx->streams[items[j].slot].clock += items[j].count;
+            ctx->stats.windowed_streams++;
          }
       }
-      std::fprintf(stderr, "[nfcgpu] speculative lanes: %zu, %llu samples as they last ran; live in the end: %llu lanes, %llu samples (%.1f %%); submission: %llu samples\n", ws.size(),
-                   (unsigned long long)all, (unsigned long long)liveLanes, (unsigned long long)live, all ? 100.0 * (double)live / (double)all : 0.0, (unsigned long long)totalSamples);
-   }
 
-   ctx->stats.windows += nWindows + nJobs;
-   ctx->stats.samples += totalSamples;
-   ctx->dirty = true;
+      ctx->stats.fallback_streams += fallback.size();
 
-   std::vector<WindowedItem> fallback;
+      mark("return");
 
-   for (uint32_t j = 0; j < nJobs; j++)
-   {
-      if (jobs[j].status & NFC_JOB_INVALID)
-         fallback.push_back(items[j]);
-      else
+      if (!fallback.empty())
       {
-         ctx->streams[items[j].slot].clock += items[j].count;
-         ctx->stats.windowed_streams++;
+         ctx->stats.samples -= 0; /* launch_demod counts the samples of the streams it decodes */
+         uint64_t again = 0;
+         for (const WindowedItem &it: fallback)
+            again += it.count;
+         ctx->stats.samples -= again;
+         *done = true;
+         return launch_sequential(ctx, T.config, fallback, T.stride);
       }
+
+      *done = true;
+      return NFCGPU_OK;
    }
-
-   ctx->stats.fallback_streams += fallback.size();
-
-   mark("return");
-
-   if (!fallback.empty())
-   {
-      ctx->stats.samples -= 0; /* launch_demod counts the samples of the streams it decodes */
-      uint64_t again = 0;
-      for (const WindowedItem &it: fallback)
-         again += it.count;
-      ctx->stats.samples -= again;
-      return launch_sequential(ctx, config, fallback, stride);
    }
 
    return NFCGPU_OK;
 }
+
+/* advance the pending tail by a state if it can go on (`block`: wait until it can); done or failed, it leaves the context */
+int tail_advance(nfcgpu_ctx *ctx, bool block)
+{
+   WindowedTail *T = ctx->tail;
+   if (!T)
+      return NFCGPU_OK;
+
+   bool done = false;
+   const int rc = tail_step(ctx, *T, block, &done);
+
+   if (rc != NFCGPU_OK || done)
+   {
+      /* Whatever way the tail ends while the side stream may still be running kernels of a pass (a launch that failed after the
+       * fork, an event that could not be recorded): the side stream is waited for before anyone reuses the staging slot or the
+       * lane buffers it reads, and the events of the pass go back to the pool. */
+      if (T->sideRunning)
+         (void)hipStreamSynchronize(ctx->side);
+      if (rc != NFCGPU_OK)
+         (void)hipStreamSynchronize(ctx->stream);
+      for (hipEvent_t e: T->passEvents)
+         ctx->eventPool.push_back(e);
+      if (T->ready)
+         ctx->eventPool.push_back(T->ready);
+      if (T->slot)
+         stage_release(ctx, T->slot);
+      ctx->tail = nullptr;
+      delete T;
+   }
+
+   return rc;
+}
+
+/* complete the pending tail, finish included: what every entry point does first, a submission that runs its front under the
+ * tail excepted. An error met in the tail is returned here, by the call that completes it. */
+int settle_tail(nfcgpu_ctx *ctx)
+{
+   while (ctx->tail)
+   {
+      const int rc = tail_advance(ctx, true);
+      if (rc)
+         return rc;
+   }
+
+   return NFCGPU_OK;
+}
+
+/* ... as the first thing an entry point of the C ABI does */
+int settle_entry(nfcgpu_ctx *ctx)
+{
+   if (!ctx->tail)
+      return NFCGPU_OK;
+
+   HIP_TRY(ctx, hipSetDevice(ctx->device));
+   return settle_tail(ctx);
+}
+
+#define SETTLE_FIRST(ctx)                            \
+   do                                                \
+   {                                                 \
+      if (ctx)                                       \
+      {                                              \
+         const int settled__ = settle_entry(ctx);    \
+         if (settled__)                              \
+            return settled__;                        \
+      }                                              \
+   } while (0)
+
+/* the front of the new submission under the pending tail? Only when it continues the very streams of the pending one. */
+bool may_overlap(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedItem> &items)
+{
+   const WindowedTail *T = ctx->tail;
+
+   if (!T || !T->deferred || !ctx->pipeline || ctx->noSecondSet || ctx->inBlocks || !ctx->front || !ctx->wShadow.ptr || T->config != config || T->items.size() != items.size())
+      return false;
+
+   for (size_t i = 0; i < items.size(); i++)
+      if (items[i].slot != T->items[i].slot)
+         return false;
+
+   return true;
+}
+
+/* the two sets of the buffers a front writes and a tail still reads change places */
+void swap_front_sets(nfcgpu_ctx *ctx)
+{
+   nfcgpu_ctx::DevBuf *mine[] = {&ctx->wRepairs, &ctx->wJobs, &ctx->wChunks, &ctx->wPoints, &ctx->wSeams, &ctx->wChunkEdge, &ctx->wTiles, &ctx->wTileStats, &ctx->wCounters,
+                                 &ctx->wRepairsEnv, &ctx->wPlanes, &ctx->wPlaneChunks, &ctx->wPlanesStale};
+
+   for (size_t i = 0; i < sizeof(mine) / sizeof(mine[0]); i++)
+      std::swap(*mine[i], ctx->otherSet[i]);
+}
+
+/* One submission of `items` (all of configuration `config`, `stride` floats per sample, data resident on the device)
+ * through scan -> windows -> windowed decode -> chain -> finish; streams the path cannot vouch for (samples off the
+ * int16 grid, a seam that did not verify, no settled chain) are then decoded sequentially from their untouched state.
+ *
+ * It has a front - tables, scan, seam rounds, planes, tile flags: a function of the samples and of the front-end state the
+ * streams start from - and a back: windows, decode passes, chain, finish. The back's own end (WindowedTail) may stay pending
+ * when the call returns; a submission that continues the same streams then runs its front under it, on ctx->front, from the
+ * shadow states the pending submission's back has left for it (nfc_shadow_kernel), and once the tail is done has the shadows
+ * compared with what the finish really wrote: a front that started from anything else is walked again from the true state. */
+int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedItem> &items, uint32_t stride)
+{
+   const auto entered = std::chrono::steady_clock::now(); /* (the stage log counts the host's tables from here) */
+   const uint32_t nJobs = (uint32_t)items.size();
+   const NfcConfig &cfg = ctx->configs[config];
+   int rc;
+
+   /* NFCGPU_WINDOW_DEBUG: where the time of a submission goes (synchronises at every mark) */
+   const bool debugStages = std::getenv("NFCGPU_WINDOW_DEBUG") != nullptr;
+
+   bool under = false; /* the front runs under the pending tail */
+
+   if (ctx->tail)
+   {
+      under = !debugStages && may_overlap(ctx, config, items);
+
+      if (!under && (rc = settle_tail(ctx)))
+         return rc;
+   }
+
+   if (debugStages && ctx->pipeline && !ctx->inBlocks)
+      std::fprintf(stderr, "[nfcgpu] the stage log is of unpipelined submissions: with NFCGPU_WINDOW_DEBUG set every submission is complete when its call returns\n");
+
+   /* A work buffer the device cannot give (NFCGPU_ENOMEM from grow()) is not the end of a submission as long as nothing of the
+    * streams has been touched - which holds up to the finish: the scan and the lanes only read the streams' state. The
+    * submission is then decoded a quarter of its length at a time (a quarter of every work buffer), and if that does not fit
+    * either by the sequential kernels, which need none. Any other error is the caller's. */
+   auto withoutTheMemory = [&](int code) -> int {
+      if (code != NFCGPU_ENOMEM)
+         return code;
+
+      (void)hipGetLastError();
+
+      uint32_t longest = 0;
+      for (const WindowedItem &it: items)
+         longest = it.count > longest ? it.count : longest;
+
+      const uint32_t quarter = longest / 4u / NFC_SCAN_POINT * NFC_SCAN_POINT;
+
+      if (!ctx->inBlocks && quarter >= 65536u && quarter >= ctx->windowedMinSamples)
+         return run_in_blocks(ctx, config, items, stride, quarter);
+
+      ctx->stats.fallback_streams += nJobs;
+      return launch_sequential(ctx, config, items, stride);
+   };
+
+   NfcScanParams sp;
+   {
+      float corr = 3.0e38f;
+      if (cfg.enabled & 1u) corr = cfg.corrThreshold[0] < corr ? cfg.corrThreshold[0] : corr;
+      if (cfg.enabled & 4u) corr = cfg.corrThreshold[2] < corr ? cfg.corrThreshold[2] : corr;
+      if (cfg.enabled & 8u) corr = cfg.corrThreshold[3] < corr ? cfg.corrThreshold[3] : corr;
+      sp.rangeK = corr < 1.0e30f ? 0.49f * corr : 3.0e38f;
+      sp.edgeK = (cfg.enabled & 2u) ? 0.99f * cfg.minDepth[1] : 3.0e38f;
+      float deep = 1.0f;
+      for (int t = 0; t < 4; t++)
+         if ((cfg.enabled >> t) & 1u)
+            deep = cfg.maxDepth[t] < deep ? cfg.maxDepth[t] : deep;
+      sp.deepK = 0.98f * deep;
+      sp.chunkSamples = ctx->scanChunk;
+      sp.warmSamples = ctx->scanWarm;
+      sp.soloSamples = ctx->soloSamples;
+      sp.offGridAlone = 1u;
+
+      /* Every chunk pays the warm-up again, so chunks should be as long as the machine allows: one lane per chunk, and
+       * 131072 lanes (256 CUs x 4 SIMDs x 2 waves of the scan kernel's 204 registers x 64) are resident at a time.
+       * Measured on 4096 streams x 2^20 idle samples: 8192 -> 1347, 16384 -> 1673, 32768 -> 1906 GB/s. */
+      if (!ctx->scanChunkFixed)
+      {
+         uint64_t total = 0;
+         for (const WindowedItem &it: items)
+            total += it.count;
+
+         /* (round 4: a sixteenth of that is enough lanes. What a submission of 2^29 samples - 512 busy streams, an eighth of
+          * config 5 - pays for are the rounds of second walks, a launch and a trip to the host each, and a chain of chunks that
+          * inherit a wrong envelope from each other is as many rounds as it has chunks: 27 rounds of 4096-sample chunks, 8 of
+          * 32768. 512 / 1024 dense streams x 2^20: 352 -> 321 ms per step.) */
+         uint64_t chunk = total / ctx->scanLanes / NFC_SCAN_POINT * NFC_SCAN_POINT;
+         if (chunk > 32768u)
+            chunk = 32768u;
+         if (chunk > sp.chunkSamples)
+            sp.chunkSamples = (uint32_t)chunk;
+
+         /* A small submission is one a caller waits for (a capture, a receiver's block): what counts is the time of the
+          * longest walk, chunk + warm-up at ~0.4 us per sample and lane. Shorter chunks and a warm-up that just covers the
+          * slowest recurrence (the average: 0.995^k) cut it; seams that do not verify cost a short second walk now. */
+         if (total <= (4u << 20))
+         {
+            if (sp.chunkSamples > 4096u)
+               sp.chunkSamples = 4096u;
+            if (sp.warmSamples > 3072u)
+               sp.warmSamples = 3072u;
+         }
+      }
+   }
+
+   /* job and chunk tables */
+   std::vector<NfcScanJob> jobs(nJobs);
+   std::vector<NfcScanChunk> chunks;
+   uint32_t tiles = 0, points = 0, tilesMost = 0;
+   uint64_t totalSamples = 0;
+
+   for (uint32_t j = 0; j < nJobs; j++)
+   {
+      NfcScanJob &job = jobs[j];
+      std::memset(&job, 0, sizeof(job));
+      job.data = items[j].data;
+      job.count = items[j].count;
+      job.slot = items[j].slot;
+      job.firstChunk = (uint32_t)chunks.size();
+      job.chunks = (job.count + sp.chunkSamples - 1) / sp.chunkSamples;
+      job.firstTile = tiles;
+      job.firstPoint = points;
+      tiles += (job.count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE;
+      tilesMost = std::max(tilesMost, (job.count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE);
+      points += job.count / NFC_SCAN_POINT + 1;
+      totalSamples += job.count;
+
+      for (uint32_t k = 0; k < job.chunks; k++)
+         chunks.push_back(NfcScanChunk {j, k});
+   }
+
+   /* Lanes inside busy signal: NFC_WINDOW_CUT samples apart when the submission is small (every lane is parallelism),
+    * further apart - fewer warm-ups, fewer hand-overs to go wrong - when that still leaves several lanes per wave slot
+    * of the machine (NFCGPU_LANES_WANTED, default 16384 = 8 per slot of 256 CUs x 8 waves) */
+   {
+      uint64_t cut = ctx->lanesWanted ? totalSamples / ctx->lanesWanted : 0u;
+      cut = cut / NFC_SCAN_POINT * NFC_SCAN_POINT;
+      cut = cut < NFC_WINDOW_CUT ? NFC_WINDOW_CUT : (cut > ctx->cutMax ? ctx->cutMax : cut);
+
+      for (NfcScanJob &job: jobs)
+         job.cut = (uint32_t)cut;
+   }
+
+   const uint32_t nChunks = (uint32_t)chunks.size();
+   const uint32_t finalLaneSlot = (nJobs + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
+   const uint32_t firstWindowSlot = 2 * finalLaneSlot;
+
+   /* The buffers the front writes and the tail still reads. Under a pending tail the front takes the second set of them (grown
+    * here to everything the front may ask for, so that nothing is grown while it runs); a second set the device cannot give
+    * means no overlap for this context - never the fallbacks of withoutTheMemory. */
+   auto growFront = [&](bool all) -> int {
+      int r;
+      if ((r = grow(ctx, ctx->wJobs, sizeof(NfcScanJob) * nJobs)) || (r = grow(ctx, ctx->wChunks, sizeof(NfcScanChunk) * nChunks)) ||
+          (r = grow(ctx, ctx->wPoints, sizeof(NfcScanPoint) * (size_t)points)) || (r = grow(ctx, ctx->wSeams, sizeof(NfcScanSeam) * nChunks)) ||
+          (r = grow(ctx, ctx->wChunkEdge, 4 * (size_t)nChunks)) || (r = grow(ctx, ctx->wTiles, 4 * (size_t)tiles)) ||
+          (r = grow(ctx, ctx->wTileStats, sizeof(NfcScanTile) * (size_t)tiles)) ||
+          (r = grow(ctx, ctx->wCounters, 256)) || (r = grow(ctx, ctx->wRepairs, sizeof(NfcScanChunk) * nChunks)) ||
+          (r = grow(ctx, ctx->wRepairsEnv, sizeof(NfcScanChunk) * nChunks)))
+         return r;
+      if (all && ((r = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) ||
+                  (r = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * (size_t)std::max(nChunks, points))) || (r = grow(ctx, ctx->wPlanesStale, 4u * (size_t)nChunks))))
+         return r;
+      return NFCGPU_OK;
+   };
+
+   if (under)
+   {
+      swap_front_sets(ctx);
+      ctx->growingSecond = true;
+      rc = growFront(true);
+      ctx->growingSecond = false;
+
+      if (rc)
+      {
+         (void)hipGetLastError();
+         swap_front_sets(ctx);
+         under = false;
+         if (rc == NFCGPU_ENOMEM)
+            ctx->noSecondSet = true;
+         const int settled = settle_tail(ctx);
+
+         /* (what was given of the second set before the device ran out goes back: it must not be what a later growth of the lane
+          * buffers finds missing) */
+         if (ctx->noSecondSet)
+            for (nfcgpu_ctx::DevBuf &b: ctx->otherSet)
+            {
+               if (b.ptr)
+                  (void)hipFree(b.ptr);
+               b.ptr = nullptr;
+               b.bytes = 0;
+            }
+
+         if (settled)
+            return settled;
+         if (rc != NFCGPU_ENOMEM)
+            return rc;
+         ctx->lastError.clear();
+      }
+   }
+
+   if (!under && (rc = growFront(false)))
+      return withoutTheMemory(rc);
+
+   uint32_t *counters = (uint32_t *)ctx->wCounters.ptr;
+
+   NfcScanArgs A;
+   std::memset(&A, 0, sizeof(A));
+   A.jobs = (NfcScanJob *)ctx->wJobs.ptr;
+   A.nJobs = nJobs;
+   A.chunks = (const NfcScanChunk *)ctx->wChunks.ptr;
+   A.nChunks = nChunks;
+   A.stride = stride;
+   A.params = sp;
+   A.states = under ? (const NfcStreamState *)ctx->wShadow.ptr : ctx->dStates;
+   A.points = (NfcScanPoint *)ctx->wPoints.ptr;
+   A.seams = (NfcScanSeam *)ctx->wSeams.ptr;
+   A.chunkEdge = (uint32_t *)ctx->wChunkEdge.ptr;
+   A.tiles = (uint32_t *)ctx->wTiles.ptr;
+   A.tileStats = (NfcScanTile *)ctx->wTileStats.ptr;
+   A.finalLaneSlot = finalLaneSlot;
+   A.firstWindowSlot = firstWindowSlot;
+   A.windowCount = counters;
+   A.rerunCount = counters + 1;
+   A.runCount = counters + 2;
+   A.runNext = counters + 3;
+   A.repairs = (NfcScanChunk *)ctx->wRepairs.ptr;
+   A.repairCount = counters + 7;
+   A.repairsEnv = ctx->envelopeMax ? (NfcScanChunk *)ctx->wRepairsEnv.ptr : nullptr; /* (NFCGPU_ENVELOPE_KERNEL=0: one list, one kernel) */
+   A.repairEnvCount = counters + 9;
+   A.saveNext = counters + 8;
+
+   const NfcConfig *dCfg = ctx->dConfigs + config;
+
+   auto stageBegan = entered;
+   auto mark = [&](const char *what) {
+      if (!debugStages)
+         return;
+      (void)hipStreamSynchronize(ctx->stream);
+      const auto now = std::chrono::steady_clock::now();
+      std::fprintf(stderr, "[nfcgpu] windowed stage %-10s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - stageBegan).count());
+      stageBegan = now;
+   };
+
+   /* (a grid has at most 65535 blocks in y: beyond 2^24 tiles in one job the kernel strides) */
+   const uint32_t tilesGridY = (tilesMost + 255) / 256 > 65535u ? 65535u : (tilesMost + 255) / 256;
+
+   bool routed = false; /* the front has handed the whole submission to somebody else (blocks, quarters, the sequential kernels): its result is the call's */
+
+   /* ---- the front: on `fs`, from A.states. `beneath`: under the pending tail, which is advanced while the front's host waits last;
+    * `redo`: walked again after the comparison (the statistics have counted its samples and second walks) ---- */
+   auto front = [&](hipStream_t fs, bool beneath, bool redo) -> int {
+      /* Whatever way the front is left while its stream is not the context's own: nobody reuses what it reads or writes while it runs */
+      struct FrontGuard
+      {
+         hipStream_t fs;
+         bool armed;
+         ~FrontGuard()
+         {
+            if (armed)
+               (void)hipStreamSynchronize(fs);
+         }
+      } frontGuard {fs, beneath};
+
+      /* a host wait of the front: under a pending tail the host goes on with that instead of sleeping */
+      auto waitFront = [&]() -> int {
+         if (!beneath)
+         {
+            HIP_TRY(ctx, hipStreamSynchronize(fs));
+            return NFCGPU_OK;
+         }
+
+         HIP_TRY(ctx, hipEventRecord(ctx->frontEvent, fs));
+
+         for (;;)
+         {
+            int r = tail_advance(ctx, false);
+            if (r)
+               return r;
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+            HIP_TRY(ctx, hipEventSynchronize(ctx->frontEvent)); /* (synchronous streams: the tail has been given its turn, the front's work is done) */
+            break;
+#else
+            const hipError_t q = hipEventQuery(ctx->frontEvent);
+            if (q == hipSuccess)
+               break;
+            if (q != hipErrorNotReady)
+               return fail(ctx, NFCGPU_EHIP, "hipEventQuery(ctx->frontEvent)", q);
+            if (!ctx->tail)
+            {
+               HIP_TRY(ctx, hipEventSynchronize(ctx->frontEvent));
+               break;
+            }
+            std::this_thread::sleep_for(std::chrono::microseconds(20)); /* (two events to look at, milliseconds apart: no need to spin) */
+#endif
+         }
+
+         return NFCGPU_OK;
+      };
+
+      auto leave = [&](int code) -> int {
+         routed = true;
+         return code;
+      };
+
+      /* (the front leaves the submission to somebody else: whatever is pending is completed first, and the front's stream is idle - callers are behind a wait) */
+      auto handOver = [&]() -> int {
+         if (beneath)
+         {
+            (void)hipStreamSynchronize(fs);
+            return settle_tail(ctx);
+         }
+         return NFCGPU_OK;
+      };
+
+      auto noMemory = [&](int code) -> int {
+         const int handed = handOver();
+         return leave(handed ? handed : withoutTheMemory(code));
+      };
+
+      auto inBlocks = [&]() -> int {
+         const int handed = handOver();
+         return leave(handed ? handed : run_in_blocks(ctx, config, items, stride));
+      };
+
+      A.planes = nullptr;
+      A.planesStale = nullptr;
+
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->wJobs.ptr, jobs.data(), sizeof(NfcScanJob) * nJobs, hipMemcpyHostToDevice, fs));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->wChunks.ptr, chunks.data(), sizeof(NfcScanChunk) * nChunks, hipMemcpyHostToDevice, fs));
+      HIP_TRY(ctx, hipMemsetAsync(counters, 0, 256, fs));
+
+      /* under the tail: not before the pending submission's first pass is over (the event its chain state waits for) - that pass has
+       * the device to itself -, which is also behind the shadow states this front starts from */
+      if (beneath && ctx->tail)
+         HIP_TRY(ctx, hipStreamWaitEvent(fs, ctx->tail->ready, 0));
+
+      mark("tables");
+
+      /* scan */
+      ProfiledLaunch pl {nullptr, nullptr};
+      record_span(ctx, ctx->timedScan, pl, true, fs);
+      hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_scan_kernel), dim3((nChunks + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, A);
+      HIP_TRY(ctx, hipGetLastError());
+      record_span(ctx, ctx->timedScan, pl, false, fs);
+      if (!redo)
+         ctx->stats.scan_samples += totalSamples;
+
+      mark("scan");
+
+      /* a first run of the tile tests: how busy is each stream? Only a small submission is routed by that (below: `small`); a large
+       * one gets its tile flags once, when the envelopes they are formed from are the true ones (3.8 ms for the 67 M tiles of config 5) */
+      if (nJobs < NFC_LANES && !ctx->inBlocks)
+      {
+         hipLaunchKernelGGL(nfc_tiles_kernel, dim3(nJobs, tilesGridY), dim3(256), 0, fs, dCfg, A, tilesMost);
+         HIP_TRY(ctx, hipGetLastError());
+      }
+
+      /* The front-end planes (below) are a walk of every chunk from its verified start state: 69 GB of stores for config 5, 32 ms
+       * of a device that the rounds of second walks after the first leave nearly idle (a few thousand chunks each, as long as
+       * their longest chain). Round 5: for a large submission that walk is started on a stream of its own (lowest priority) as soon as the first round's
+       * second walks are queued - by then nine chunks in ten start from their true state -, the seam check and the envelope
+       * walks note every start state they rewrite from then on (NfcScanArgs::planesStale), and those chunks' planes are written
+       * again when the rounds are over. */
+      const bool planesBeside = ctx->planesBeside && ctx->low != nullptr && totalSamples > (4u << 20);
+      bool planesStarted = false;
+
+      struct PlanesGuard
+      {
+         nfcgpu_ctx *ctx;
+         bool running;
+         ~PlanesGuard()
+         {
+            if (running)
+               (void)hipStreamSynchronize(ctx->low); /* (whatever way the function is left: nobody reuses what the walk reads or writes while it runs) */
+         }
+      } planesGuard {ctx, false};
+
+      if (planesBeside)
+      {
+         if ((rc = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) || (rc = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * nChunks)) ||
+             (rc = grow(ctx, ctx->wPlanesStale, 4u * (size_t)nChunks)))
+            return noMemory(rc);
+
+         HIP_TRY(ctx, hipMemsetAsync(ctx->wPlanesStale.ptr, 0, 4u * (size_t)nChunks, fs));
+      }
+
+      /* seams: chunks that did not start from the true state are walked again, a round at a time */
+
+      for (uint32_t round = 0;; round++)
+      {
+         if (debugStages && std::atoi(std::getenv("NFCGPU_WINDOW_DEBUG")) >= 4)
+         {
+            /* which fields keep seams from verifying (host-side look at the records the seam check is about to judge) */
+            std::vector<NfcScanSeam> sm(nChunks);
+            if ((rc = waitFront()))
+               return rc;
+            HIP_TRY(ctx, hipMemcpy(sm.data(), ctx->wSeams.ptr, sizeof(NfcScanSeam) * nChunks, hipMemcpyDeviceToHost));
+            uint32_t n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (uint32_t j = 0; j < nJobs; j++)
+               for (uint32_t k = 1; k < jobs[j].chunks; k++)
+               {
+                  const NfcScanPoint &a = sm[jobs[j].firstChunk + k].start, &b = sm[jobs[j].firstChunk + k - 1].end;
+                  const bool env = std::memcmp(&a.env, &b.env, 4) != 0 || a.pulseFilter != b.pulseFilter;
+                  const bool n1 = std::memcmp(&a.n1, &b.n1, 4) != 0, mdev = std::memcmp(&a.mdev, &b.mdev, 4) != 0, avg = std::memcmp(&a.avg, &b.avg, 4) != 0;
+                  const bool peak = std::memcmp(&a.edgePeak, &b.edgePeak, 4) != 0, zone = ((a.zone ^ b.zone) & 0xFFu) != 0;
+                  const bool time = (a.zone & 0x100u) && (b.zone & 0x100u) && a.edgeTime != b.edgeTime;
+                  n[0] += env; n[1] += n1; n[2] += mdev; n[3] += avg; n[4] += peak; n[5] += zone; n[6] += time;
+                  n[7] += (n1 || mdev || avg || peak || zone) ? 1u : 0u;
+               }
+            std::fprintf(stderr, "[nfcgpu]    before round %u, seams that differ in: envelope / counter %u, n1 %u, deviation %u, average %u, edge peak %u, zone %u, known edge times %u; in anything but the envelope %u\n",
+                         round, n[0], n[1], n[2], n[3], n[4], n[5], n[6], n[7]);
+         }
+
+         HIP_TRY(ctx, hipMemsetAsync(counters + 7, 0, 4, fs));
+         HIP_TRY(ctx, hipMemsetAsync(counters + 9, 0, 4, fs));
+         hipLaunchKernelGGL(nfc_seams_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, fs, A, round == 0 ? 1u : 0u);
+         HIP_TRY(ctx, hipGetLastError());
+
+         /* chunks to walk again: every recurrence of them (A.repairs), the envelope tracker alone (A.repairsEnv: listed apart by
+          * the seam check when the envelope kernel is on) */
+         uint32_t *word = ctx->frontHost; /* (pinned: the copy does not hold the host, which has a tail to advance) */
+         HIP_TRY(ctx, hipMemcpyAsync(word, counters + 7, 12, hipMemcpyDeviceToHost, fs));
+
+         /* (a small submission: how busy are its streams? the tile tests have counted) */
+         const bool small = round == 0 && nJobs < NFC_LANES && !ctx->inBlocks;
+         if (small)
+            HIP_TRY(ctx, hipMemcpyAsync(jobs.data(), ctx->wJobs.ptr, sizeof(NfcScanJob) * nJobs, hipMemcpyDeviceToHost, fs));
+
+         if ((rc = waitFront()))
+            return rc;
+         const uint32_t whole = word[0], alone = word[2];
+         const uint32_t repairs = whole + alone;
+
+         /* A few long busy streams: the passes the chain needs grow with the length of the submission (a frame that changes
+          * the protocol timing is learnt one generation per pass), so it is decoded in blocks, each settled before the next.
+          * Nothing has been touched yet (the scan only reads). */
+         if (small)
+         {
+            uint32_t longest = 0;
+            bool busy = false;
+
+            for (uint32_t j = 0; j < nJobs; j++)
+            {
+               const uint64_t nTiles = ((uint64_t)jobs[j].count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE;
+               busy = busy || (uint64_t)jobs[j].busyTiles * 100u > nTiles * ctx->busyPercent;
+               longest = jobs[j].count > longest ? jobs[j].count : longest;
+            }
+
+            if (busy && longest > ctx->blockSamples)
+               return inBlocks();
+         }
+
+         if (debugStages)
+            std::fprintf(stderr, "[nfcgpu]    seams round %u: %u chunks to walk again\n", round, repairs);
+
+         if (!repairs)
+            break;
+
+         /* The chunks whose envelope tracker alone started wrong - from the second round on that is all of them: chains of chunks
+          * that inherit a wrong envelope from each other, a chunk per round - go to a kernel that does nothing else, a wavefront
+          * per chunk (nfc_envelope.hpp): a round then costs the tracker's own latency over one chunk instead of the scan kernel's
+          * row machinery over it (9 ms of 32768 samples, however short the list). A list too long for a wave a chunk to pay (the
+          * first round of a large submission: a quarter of its chunks, the scan kernel's 64 chunks per wave are the better use
+          * of the machine) stays with the scan kernel's envelope-only branch (NFCGPU_ENVELOPE_KERNEL: the longest list the
+          * envelope kernel is given). */
+         if (debugStages && alone && alone <= ctx->envelopeMax)
+            std::fprintf(stderr, "[nfcgpu]    ... %u of them the envelope tracker's alone, by the envelope kernel\n", alone);
+
+         ProfiledLaunch pr {nullptr, nullptr};
+         record_span(ctx, ctx->timedScan, pr, true, fs);
+
+         const bool byWaves = alone && alone <= ctx->envelopeMax;
+
+         if (whole || (alone && !byWaves))
+         {
+            /* the scan kernel: the chunks walked whole, and a list of envelope-only ones too long for a wave each, in one launch */
+            NfcScanArgs R = A;
+            R.chunks = A.repairs;
+            R.nChunks = whole;
+            R.chunksMore = byWaves ? nullptr : A.repairsEnv;
+            R.nChunksMore = byWaves ? 0u : alone;
+
+            const uint32_t listedNow = R.nChunks + R.nChunksMore;
+
+            hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_scan_kernel), dim3((listedNow + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, R);
+            HIP_TRY(ctx, hipGetLastError());
+         }
+
+         if (byWaves)
+         {
+            NfcScanArgs R = A;
+            R.chunks = A.repairsEnv;
+            R.nChunks = alone;
+            R.followChains = alone <= ctx->envelopeFollowMax ? 1u : 0u;
+
+            hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_envelope_kernel), dim3(alone), dim3(NFC_LANES), 0, fs, dCfg, R);
+            HIP_TRY(ctx, hipGetLastError());
+         }
+
+         record_span(ctx, ctx->timedScan, pr, false, fs);
+         if (!redo)
+            ctx->stats.scan_repairs += repairs;
+
+         if (planesBeside && round == 0)
+         {
+            /* the planes of every chunk, beside the rounds to come */
+            HIP_TRY(ctx, hipEventRecord(ctx->planesFork, fs));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->low, ctx->planesFork, 0));
+            planesGuard.running = true;
+
+            NfcScanArgs P = A;
+            P.planes = (float *)ctx->wPlanes.ptr;
+            P.chunks = (const NfcScanChunk *)ctx->wChunks.ptr; /* (the submission's chunk table as it is: the walk takes no notice of the repair marks) */
+            P.nChunks = nChunks;
+            /* a lane per piece, and the pieces of a chunk have to tile it: the largest multiple of the distance of the stored
+             * points (every lane starts from one) that is no longer than NFCGPU_PLANES_BESIDE_PIECE and divides the chunk. (Until
+             * round 6 the quotient was truncated: with a chunk that is no multiple of the piece - the default sizing gives any
+             * multiple of 512 for totals between 2^28 and 2^30 samples - the tail of every chunk that was not walked again got no
+             * planes at all.) A chunk is a multiple of the points' distance, so that distance always does. */
+            P.planesPiece = ctx->planesBesidePiece / NFC_SCAN_POINT * NFC_SCAN_POINT;
+            if (P.planesPiece > sp.chunkSamples)
+               P.planesPiece = sp.chunkSamples / NFC_SCAN_POINT * NFC_SCAN_POINT;
+            while (P.planesPiece > NFC_SCAN_POINT && sp.chunkSamples % P.planesPiece != 0u)
+               P.planesPiece -= NFC_SCAN_POINT;
+            if (P.planesPiece && sp.chunkSamples % P.planesPiece != 0u)
+               P.planesPiece = 0u; /* (a chunk that is no multiple of the points' distance: a lane per chunk, from its start) */
+            P.planesPerChunk = P.planesPiece ? sp.chunkSamples / P.planesPiece : 0u;
+
+            const uint64_t lanesOfIt = (uint64_t)nChunks * (P.planesPerChunk ? P.planesPerChunk : 1u);
+
+            ProfiledLaunch pp {nullptr, nullptr};
+            record_span(ctx, ctx->timedPlanes, pp, true, ctx->low);
+            hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)((lanesOfIt + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->low, dCfg, P);
+            HIP_TRY(ctx, hipGetLastError());
+            record_span(ctx, ctx->timedPlanes, pp, false, ctx->low);
+            HIP_TRY(ctx, hipEventRecord(ctx->planesJoin, ctx->low));
+
+            planesStarted = true;
+            A.planesStale = (uint32_t *)ctx->wPlanesStale.ptr; /* from the next round on */
+         }
+      }
+      hipLaunchKernelGGL(nfc_tiles_kernel, dim3(nJobs, tilesGridY), dim3(256), 0, fs, dCfg, A, tilesMost);
+      HIP_TRY(ctx, hipGetLastError());
+
+      mark("seams");
+
+      /* The wave decoder takes the front end's results per sample instead of walking it again: a second walk of every
+       * chunk from its verified start state (the repair form of the scan: no warm-up) writes them. */
+      if (planesStarted)
+      {
+         /* the walk over all chunks has run beside the rounds: the chunks whose start state changed under it, again */
+         HIP_TRY(ctx, hipStreamWaitEvent(fs, ctx->planesJoin, 0));
+         planesGuard.running = false; /* (the main stream now waits for it) */
+
+         HIP_TRY(ctx, hipMemsetAsync(counters + 11, 0, 4, fs));
+         hipLaunchKernelGGL(nfc_planes_stale_kernel, dim3((nChunks + 255) / 256), dim3(256), 0, fs, A, (const NfcScanChunk *)ctx->wChunks.ptr, nChunks,
+                            (NfcScanChunk *)ctx->wPlaneChunks.ptr, counters + 11);
+         HIP_TRY(ctx, hipGetLastError());
+
+         uint32_t &again = ctx->frontHost[4];
+         HIP_TRY(ctx, hipMemcpyAsync(ctx->frontHost + 4, counters + 11, 4, hipMemcpyDeviceToHost, fs));
+         if ((rc = waitFront()))
+            return rc;
+
+         A.planes = (float *)ctx->wPlanes.ptr;
+         A.planesStale = nullptr;
+
+         if (debugStages)
+            std::fprintf(stderr, "[nfcgpu]    planes written beside the rounds; %u chunks of %u again\n", again, nChunks);
+
+         if (again)
+         {
+            NfcScanArgs P = A;
+            /* (a stored point per lane - 512 samples, from the points the rounds have left true -: a few thousand chunks a lane each
+             * would take as long as one chunk's walk, 12 ms, with the device all but idle) */
+            P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
+            P.nChunks = again;
+            P.planesPiece = NFC_SCAN_POINT;
+            P.planesPerChunk = sp.chunkSamples / NFC_SCAN_POINT;
+
+            ProfiledLaunch pp {nullptr, nullptr};
+            record_span(ctx, ctx->timedPlanes, pp, true, fs);
+            hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)(((uint64_t)again * P.planesPerChunk + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, fs, dCfg, P);
+            HIP_TRY(ctx, hipGetLastError());
+            record_span(ctx, ctx->timedPlanes, pp, false, fs);
+         }
+
+         mark("planes");
+      }
+      else
+      {
+         /* A small submission - one a caller waits for - is walked a lane per stored point instead of a lane per chunk: 512 samples
+          * instead of 4096 on the way of everything that follows (NFCGPU_PLANES_PIECE; a short capture: 1.1 -> 0.2 ms) */
+         const uint32_t piece = totalSamples <= (4u << 20) ? ctx->planesPiece / NFC_SCAN_POINT * NFC_SCAN_POINT : 0u;
+
+         std::vector<NfcScanChunk> all;
+
+         if (piece)
+         {
+            for (uint32_t j = 0; j < nJobs; j++)
+               for (uint32_t i = 0; i * piece < jobs[j].count; i++)
+                  all.push_back(NfcScanChunk {j, i | NFC_CHUNK_REPAIR});
+         }
+         else
+         {
+            all = chunks;
+            for (NfcScanChunk &c: all)
+               c.index |= NFC_CHUNK_REPAIR;
+         }
+
+         const uint32_t nPlaneLanes = (uint32_t)all.size();
+
+         if ((rc = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) || (rc = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * all.size())))
+         {
+            /* (the planes are 16 bytes per sample of the submission: 64 GiB for 4096 streams x 2^20) */
+            return noMemory(rc);
+         }
+
+         HIP_TRY(ctx, hipMemcpyAsync(ctx->wPlaneChunks.ptr, all.data(), sizeof(NfcScanChunk) * all.size(), hipMemcpyHostToDevice, fs));
+
+         A.planes = (float *)ctx->wPlanes.ptr;
+
+         NfcScanArgs P = A;
+         P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
+         P.nChunks = nPlaneLanes;
+         P.planesPiece = piece;
+
+         ProfiledLaunch pp {nullptr, nullptr};
+         record_span(ctx, ctx->timedPlanes, pp, true, fs);
+         hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((nPlaneLanes + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, P);
+         HIP_TRY(ctx, hipGetLastError());
+         record_span(ctx, ctx->timedPlanes, pp, false, fs);
+         if ((rc = waitFront()))
+            return rc; /* (the chunk list is a local) */
+
+         mark("planes");
+      }
+
+      frontGuard.armed = false;
+      return NFCGPU_OK;
+   };
+
+   if (under)
+   {
+      rc = front(ctx->front, true, false);
+      if (rc || routed)
+         return rc;
+
+      ctx->stats.pipelined_submissions++;
+
+      /* the tail, finish and any sequential fallback of its invalid jobs included; then the main stream takes the front's work in */
+      if ((rc = settle_tail(ctx)))
+      {
+         (void)hipStreamSynchronize(ctx->front);
+         return rc;
+      }
+
+      HIP_TRY(ctx, hipEventRecord(ctx->frontEvent, ctx->front));
+      HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->frontEvent, 0));
+
+      /* exact or not taken: what the finish really left in the slots against the shadow states the front started from */
+      NfcShadowArgs S;
+      std::memset(&S, 0, sizeof(S));
+      S.jobs = A.jobs;
+      S.nJobs = nJobs;
+      S.real = ctx->dStates;
+      S.shadow = (NfcStreamState *)ctx->wShadow.ptr;
+      S.ctl = (uint32_t *)ctx->wShadowCtl.ptr;
+
+      S.points = A.points;
+      S.renameSeams = A.seams;
+      S.renameEdge = A.chunkEdge;
+
+      HIP_TRY(ctx, hipMemsetAsync(S.ctl, 0, 64, ctx->stream));
+      hipLaunchKernelGGL(nfc_shadow_compare_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, S);
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->tailHost + 16, S.ctl, 64, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+      const uint32_t differ = ctx->tailHost[16], zeroed = ctx->tailHost[26];
+      A.states = ctx->dStates;
+
+      if (ctx->pipelineReport && !differ)
+         std::fprintf(stderr, "[nfcgpu] pipelined front: %u streams ended on a zeroed edge time (put right in the records), none differs otherwise\n", zeroed);
+
+      if (!differ)
+         ctx->stats.pipeline_zeroed_edges += zeroed;
+
+      if (zeroed && !differ)
+      {
+         /* (a carrier frame after the tracker last moved: NfcShadowArgs) */
+         hipLaunchKernelGGL(nfc_shadow_rename_kernel, dim3(nJobs), dim3(64), 0, ctx->stream, S);
+         HIP_TRY(ctx, hipGetLastError());
+      }
+
+      if (differ)
+      {
+         /* streams that did not end where their front-end records said (a stream the sequential kernels decoded, say): the front
+          * again, unpipelined, from the true state */
+         const uint32_t *f = ctx->tailHost + 16;
+         ctx->stats.pipeline_refronts += differ;
+
+         if (ctx->pipelineReport)
+            std::fprintf(stderr, "[nfcgpu] pipelined front redone: %u streams differ from their shadow state otherwise than by a zeroed edge time (clock %u, pulse counter %u, envelope %u, n1 %u, deviation %u, average %u, "
+                                 "edge peak %u, edge time %u, carrier zone %u)\n", f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9]);
+
+         rc = front(ctx->stream, false, true);
+         if (rc || routed)
+            return rc;
+      }
+   }
+   else
+   {
+      rc = front(ctx->stream, false, false);
+      if (rc || routed)
+         return rc;
+   }
+
+   /* ---- the back: on the context's stream, the streams' own slots ---- */
+
+   /* windows (again with more room when the guess was short) */
+   uint32_t nWindows = 0;
+
+   /* lanes: a first guess (one window per 8192 samples); the window kernel reports what it needs */
+   uint32_t room = (uint32_t)(totalSamples / 8192) + 2 * nJobs + 64;
+
+   /* records per lane slot (carry lanes, final lanes, one per window); ring and frame-assembly storage per carry lane,
+    * final lane and per lane of the persistent waves that run the windows */
+   const size_t storageLanes = (size_t)firstWindowSlot; /* (a speculative window's rings live in LDS; one that runs to the end leaves a copy in the save area) */
+
+   auto growLanes = [&](uint32_t lanesWanted) -> int {
+      const size_t lanes = ((size_t)lanesWanted + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
+      int r;
+      if ((r = grow(ctx, ctx->wWindows, sizeof(NfcWindow) * lanes)) || (r = grow(ctx, ctx->wWorks, sizeof(NfcWork) * lanes)) ||
+          (r = grow(ctx, ctx->vStates, sizeof(NfcStreamState) * lanes)) || (r = grow(ctx, ctx->vCold, sizeof(NfcStreamCold) * lanes)) ||
+          (r = grow(ctx, ctx->wRunList, 4 * lanes)) ||
+          (r = grow(ctx, ctx->vRings, sizeof(float) * (size_t)kRingBlockFloats * (storageLanes / NFC_LANES))) ||
+          (r = grow(ctx, ctx->vBytes, (size_t)NFC_STREAM_BYTES * storageLanes)))
+         return r;
+      return NFCGPU_OK;
+   };
+
+   /* is there room already from an earlier, larger submission? */
+   {
+      /* (every lane buffer has to hold them: one that could not be grown last time - NFCGPU_ENOMEM, the submission then taken in
+       * quarters - must not be asked for the room its neighbours got) */
+      size_t have = ctx->wWindows.bytes / sizeof(NfcWindow);
+      have = std::min(have, ctx->wWorks.bytes / sizeof(NfcWork));
+      have = std::min(have, ctx->vStates.bytes / sizeof(NfcStreamState));
+      have = std::min(have, ctx->vCold.bytes / sizeof(NfcStreamCold));
+      have = std::min(have, ctx->wRunList.bytes / 4);
+      if (have > (size_t)firstWindowSlot + room)
+         room = (uint32_t)(have - firstWindowSlot - NFC_LANES);
+   }
+
+   if ((rc = growLanes(firstWindowSlot + room)))
+      return withoutTheMemory(rc);
+
+   /* staging sink for the lanes' chained frame records (lanes that turn out not to be live write theirs too): room
+    * for four times the frame sink, at least 64 MiB; what does not fit is reported as dropped like any overflow */
+   {
+      size_t staging = (size_t)ctx->ownSinkWords * 16;
+      if (staging < (64u << 20))
+         staging = 64u << 20;
+      if (staging > 0xFFFFFFF0ull * 4ull)
+         staging = 0xFFFFFFF0ull * 4ull;
+      if ((rc = grow(ctx, ctx->vSink, staging)) || (rc = grow(ctx, ctx->vSinkCtl, 16)))
+         return withoutTheMemory(rc);
+   }
+
+   HIP_TRY(ctx, hipMemsetAsync(ctx->vSinkCtl.ptr, 0, 16, ctx->stream));
+
+   A.windows = (NfcWindow *)ctx->wWindows.ptr;
+   A.works = (NfcWork *)ctx->wWorks.ptr;
+   A.windowRoom = room;
+   A.runList = (uint32_t *)ctx->wRunList.ptr;
+
+   /* save area for lanes that run to the end of the submission (nfc_scan_launch.h): a few per stream */
+   {
+      const uint32_t saveRoom = 2 * nJobs + 1024;
+      if ((rc = grow(ctx, ctx->vSaveRings, sizeof(float) * (size_t)(kRingBlockFloats / NFC_LANES) * saveRoom)) ||
+          (rc = grow(ctx, ctx->vSaveBytes, (size_t)NFC_STREAM_BYTES * saveRoom)))
+         return withoutTheMemory(rc);
+
+      A.saveRings = (float *)ctx->vSaveRings.ptr;
+      A.saveBytes = (uint8_t *)ctx->vSaveBytes.ptr;
+      A.saveNext = counters + 8;
+      A.saveRoom = saveRoom;
+   }
+
+   /* The shadow states a submission that continues these streams may start its front from while this one's tail is pending: the
+    * slot as the front found it, its front-end fields set from the end of the last chunk - the front end is a function of the
+    * samples, and once the rounds are over that end is the true one - the way nfc_window_lane turns a point into state. (Nobody
+    * reads the shadows of the submission before any more: its successor's front - this one - has been joined.) */
+   const bool shadows = ctx->pipeline && !ctx->inBlocks && !debugStages && ctx->deferOK && !ctx->noSecondSet && ctx->front != nullptr;
+
+   if (shadows && !ctx->wShadow.ptr)
+   {
+      if (grow(ctx, ctx->wShadow, sizeof(NfcStreamState) * (size_t)ctx->maxStreams) || grow(ctx, ctx->wShadowCtl, 64 + 4 * (size_t)ctx->maxStreams))
+      {
+         (void)hipGetLastError();
+         ctx->noSecondSet = true;
+         ctx->lastError.clear();
+      }
+   }
+
+   if (shadows && ctx->wShadow.ptr && ctx->wShadowCtl.ptr)
+   {
+      NfcShadowArgs S;
+      std::memset(&S, 0, sizeof(S));
+      S.jobs = A.jobs;
+      S.nJobs = nJobs;
+      S.seams = A.seams;
+      S.chunkEdge = A.chunkEdge;
+      S.from = ctx->dStates; /* (whatever was pending has been completed: the slots are what this submission starts from) */
+      S.shadow = (NfcStreamState *)ctx->wShadow.ptr;
+      S.spoil = ctx->spoilShadow;
+
+      hipLaunchKernelGGL(nfc_shadow_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, S);
+      HIP_TRY(ctx, hipGetLastError());
+   }
+
+   for (int attempt = 0; attempt < 2; attempt++)
+   {
+      hipLaunchKernelGGL(nfc_windows_kernel, dim3(nJobs), dim3(64), 0, ctx->stream, A);
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(&nWindows, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+      if (nWindows <= room)
+         break;
+
+      room = nWindows + NFC_LANES;
+      if ((rc = growLanes(firstWindowSlot + room)))
+         return withoutTheMemory(rc);
+
+      A.windows = (NfcWindow *)ctx->wWindows.ptr;
+      A.works = (NfcWork *)ctx->wWorks.ptr;
+         A.runList = (uint32_t *)ctx->wRunList.ptr;
+      A.windowRoom = room;
+      HIP_TRY(ctx, hipMemsetAsync(counters, 0, 4, ctx->stream));
+   }
+
+   mark("windows");
+
+   NfcLaunch real = base_launch(ctx);
+
+   NfcLaunch lanes;
+   std::memset(&lanes, 0, sizeof(lanes));
+   lanes.states = (NfcStreamState *)ctx->vStates.ptr;
+   lanes.cold = (NfcStreamCold *)ctx->vCold.ptr;
+   lanes.rings = (float *)ctx->vRings.ptr;
+   lanes.bytes = (uint8_t *)ctx->vBytes.ptr;
+   lanes.sink = (uint32_t *)ctx->vSink.ptr;
+   lanes.sinkCtl = (uint32_t *)ctx->vSinkCtl.ptr;
+   lanes.sinkWords = (uint32_t)(ctx->vSink.bytes / 4 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : ctx->vSink.bytes / 4);
+   if (ctx->stagingWords && lanes.sinkWords > ctx->stagingWords)
+      lanes.sinkWords = ctx->stagingWords; /* (NFCGPU_STAGING_WORDS: the tests make it run full) */
+   lanes.ringBlockFloats = kRingBlockFloats;
+   lanes.works = (const NfcWork *)ctx->wWorks.ptr;
+   lanes.windows = (NfcWindow *)ctx->wWindows.ptr;
+   lanes.jobs = (const NfcScanJob *)ctx->wJobs.ptr;
+   lanes.laneStats = counters + 4;
+   lanes.uniformStride = stride;
+
+   /* lanes */
+   hipLaunchKernelGGL(nfc_carry_lanes_kernel, dim3(nJobs), dim3(NFC_LANES), 0, ctx->stream, A, real, lanes, 0u);
+   HIP_TRY(ctx, hipGetLastError());
+
+   const uint32_t windowBlocks = (nWindows + NFC_LANES - 1) / NFC_LANES;
+
+
+   WindowedTail *T = new (std::nothrow) WindowedTail();
+   if (!T)
+      return fail(ctx, NFCGPU_ENOMEM, "out of host memory");
+
+   T->config = config;
+   T->stride = stride;
+   T->items = items;
+   T->A = A;
+   T->real = real;
+   T->lanes = lanes;
+   T->dCfg = dCfg;
+   T->counters = counters;
+   T->dJobs = ctx->wJobs.ptr;
+   T->nJobs = nJobs;
+   T->nWindows = nWindows;
+   T->windowBlocks = windowBlocks;
+   T->firstWindowSlot = firstWindowSlot;
+   T->finalLaneSlot = finalLaneSlot;
+   T->totalSamples = totalSamples;
+   T->debugStages = debugStages;
+   T->stageBegan = stageBegan;
+   T->ready = take_event(ctx);
+   record_span(ctx, ctx->timedWindow, T->pw, true);
+
+   ctx->tail = T;
+
+   if ((rc = tail_list(ctx, *T)))
+   {
+      ctx->tail = nullptr;
+      ctx->eventPool.push_back(T->ready);
+      delete T;
+      return rc;
+   }
+
+   /* the first pass and the chain kernel behind it */
+   while (ctx->tail && !(T->state == WindowedTail::Chain && T->pass == 0))
+      if ((rc = tail_advance(ctx, true)))
+         return rc;
+
+   /* The rest may stay pending for the next submission to run its front under (one that continues these streams; anything else
+    * completes it first) - not when the call has to have the device's answer: a block of run_in_blocks, a stage log, a caller
+    * that did not come through nfcgpu_submit_uniform. */
+   if (ctx->tail && shadows && ctx->wShadow.ptr && ctx->wShadowCtl.ptr && !std::getenv("NFCGPU_WAVE_VERIFY_REPORT") && !ctx->dumpWindows)
+   {
+      T->deferred = true;
+      return NFCGPU_OK;
+   }
+
+   return settle_tail(ctx);
+}
+
 
 /* the next staging slot, idle and at least `bytes` large */
 int stage_acquire(nfcgpu_ctx *ctx, size_t bytes, nfcgpu_ctx::StageSlot **out)
 {
    nfcgpu_ctx::StageSlot &slot = ctx->stage[ctx->stageNext];
    ctx->stageNext ^= 1u;
+
+   /* (the slot of the pending tail's submission - its turn comes round when a submission in between failed: the tail's kernels
+    * still read the rows) */
+   if (ctx->tail && ctx->tail->slot == &slot)
+   {
+      const int settled = settle_tail(ctx);
+      if (settled)
+         return settled;
+   }
 
    if (slot.busy)
    {
@@ -2005,6 +2804,8 @@ void release_workspace(nfcgpu_ctx *ctx)
       (void)hipStreamSynchronize(ctx->side);
    if (ctx->low)
       (void)hipStreamSynchronize(ctx->low);
+   if (ctx->front)
+      (void)hipStreamSynchronize(ctx->front);
 
    for (auto *list: {&ctx->timed, &ctx->timedScan, &ctx->timedWindow, &ctx->timedWave, &ctx->timedPlanes})
    {
@@ -2021,13 +2822,40 @@ void release_workspace(nfcgpu_ctx *ctx)
 
    for (nfcgpu_ctx::DevBuf *b: {&ctx->wRepairs, &ctx->wRepairsEnv, &ctx->wJobs, &ctx->wChunks, &ctx->wPoints, &ctx->wSeams, &ctx->wChunkEdge, &ctx->wTiles, &ctx->wTileStats, &ctx->wWindows, &ctx->wRunList,
                                 &ctx->wWorks, &ctx->wCounters, &ctx->vStates, &ctx->vCold, &ctx->vRings, &ctx->vBytes, &ctx->vSink, &ctx->vSinkCtl, &ctx->vSaveRings, &ctx->vSaveBytes,
-                                &ctx->wPlanes, &ctx->wPlaneChunks})
+                                &ctx->wPlanes, &ctx->wPlaneChunks, &ctx->wPlanesStale, &ctx->wShadow, &ctx->wShadowCtl})
    {
       if (b->ptr)
          (void)hipFree(b->ptr);
       b->ptr = nullptr;
       b->bytes = 0;
    }
+
+   /* (the second set of pipelined submissions) */
+   for (nfcgpu_ctx::DevBuf &b: ctx->otherSet)
+   {
+      if (b.ptr)
+         (void)hipFree(b.ptr);
+      b.ptr = nullptr;
+      b.bytes = 0;
+   }
+
+   if (ctx->tailHost)
+      (void)hipHostFree(ctx->tailHost);
+   if (ctx->tailJobs)
+      (void)hipHostFree(ctx->tailJobs);
+   ctx->tailHost = ctx->frontHost = nullptr;
+   ctx->tailJobs = nullptr;
+   ctx->tailJobsBytes = 0;
+
+   for (hipEvent_t *e: {&ctx->frontEvent, &ctx->planesFork, &ctx->planesJoin})
+   {
+      if (*e)
+         (void)hipEventDestroy(*e);
+      *e = nullptr;
+   }
+   if (ctx->front)
+      (void)hipStreamDestroy(ctx->front);
+   ctx->front = nullptr;
 
    if (ctx->epoch)
       (void)hipEventDestroy(ctx->epoch);
@@ -2217,6 +3045,10 @@ int nfcgpu_init(int device, const nfcgpu_options *options, nfcgpu_ctx **out)
    if (ctx->cutMax < NFC_WINDOW_CUT)
       ctx->cutMax = NFC_WINDOW_CUT;
    ctx->sideMode = knob("NFCGPU_SIDE_STREAM", ctx->sideMode);
+   ctx->pipeline = knob("NFCGPU_PIPELINE", 1) != 0;
+   ctx->spoilShadow = knob("NFCGPU_TEST_SPOIL_SHADOW", 0);
+   ctx->dumpWindows = tuning("NFCGPU_DUMP_WINDOWS") != nullptr;
+   ctx->pipelineReport = tuning("NFCGPU_PIPELINE_REPORT") != nullptr;
    ctx->blockSamples = knob("NFCGPU_BLOCK_SAMPLES", ctx->blockSamples) / NFC_SCAN_POINT * NFC_SCAN_POINT;
    if (ctx->blockSamples < 65536u)
       ctx->blockSamples = 65536u;
@@ -2251,6 +3083,18 @@ int nfcgpu_init(int device, const nfcgpu_options *options, nfcgpu_ctx **out)
    }
    ok = ok && hipEventCreateWithFlags(&ctx->forkEvent, hipEventDisableTiming) == hipSuccess;
    ok = ok && hipEventCreateWithFlags(&ctx->joinEvent, hipEventDisableTiming) == hipSuccess;
+   /* pipelined submissions: the stream of a front that runs under the tail of the submission before, its events, the pinned words
+    * of the read-backs */
+   ok = ok && hipStreamCreateWithFlags(&ctx->front, hipStreamNonBlocking) == hipSuccess;
+   ok = ok && hipEventCreateWithFlags(&ctx->frontEvent, hipEventDisableTiming) == hipSuccess;
+   ok = ok && hipEventCreateWithFlags(&ctx->planesFork, hipEventDisableTiming) == hipSuccess;
+   ok = ok && hipEventCreateWithFlags(&ctx->planesJoin, hipEventDisableTiming) == hipSuccess;
+   ok = ok && hipHostMalloc((void **)&ctx->tailHost, 64 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+   if (ok)
+   {
+      std::memset(ctx->tailHost, 0, 64 * sizeof(uint32_t));
+      ctx->frontHost = ctx->tailHost + 32;
+   }
 
    ok = ok && hipMalloc((void **)&ctx->dStates, sizeof(NfcStreamState) * (size_t)maxStreams) == hipSuccess;
    ok = ok && hipMalloc((void **)&ctx->dCold, sizeof(NfcStreamCold) * (size_t)maxStreams) == hipSuccess;
@@ -2301,6 +3145,8 @@ int nfcgpu_shutdown(nfcgpu_ctx *ctx)
 
    (void)hipSetDevice(ctx->device);
 
+   (void)settle_tail(ctx);
+
    if (ctx->stream)
       (void)hipStreamSynchronize(ctx->stream);
    if (ctx->side)
@@ -2336,6 +3182,8 @@ int nfcgpu_shutdown(nfcgpu_ctx *ctx)
 
 int nfcgpu_stream_open_many(nfcgpu_ctx *ctx, const nfcgpu_params *params, uint32_t count, uint32_t *first)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !first || count == 0)
       return NFCGPU_EINVAL;
 
@@ -2389,6 +3237,8 @@ int nfcgpu_stream_open(nfcgpu_ctx *ctx, const nfcgpu_params *params, uint32_t *i
 
 int nfcgpu_stream_configure(nfcgpu_ctx *ctx, uint32_t id, const nfcgpu_params *params)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !params)
       return NFCGPU_EINVAL;
 
@@ -2421,6 +3271,8 @@ int nfcgpu_stream_configure(nfcgpu_ctx *ctx, uint32_t id, const nfcgpu_params *p
 
 int nfcgpu_stream_reset(nfcgpu_ctx *ctx, uint32_t id)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -2438,6 +3290,8 @@ int nfcgpu_stream_reset(nfcgpu_ctx *ctx, uint32_t id)
 
 int nfcgpu_stream_close(nfcgpu_ctx *ctx, uint32_t id)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -2473,6 +3327,8 @@ const float *widen_i16(nfcgpu_ctx *ctx, const void *data, size_t values)
 
 int nfcgpu_submit_batch_fmt(nfcgpu_ctx *ctx, const nfcgpu_batch *b, uint32_t format)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !b || !b->stream_ids || !b->data || !b->n_samples || (b->stride != 1 && b->stride != 2) ||
        (b->location != NFCGPU_LOC_HOST && b->location != NFCGPU_LOC_DEVICE) || (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16))
       return NFCGPU_EINVAL;
@@ -2756,6 +3612,8 @@ int nfcgpu_magnitude(nfcgpu_ctx *ctx, const float *iq, uint64_t n, float *out, u
 
 int nfcgpu_magnitude_fmt(nfcgpu_ctx *ctx, const void *iq, uint64_t n, float *out, uint32_t location, uint32_t format)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !iq || !out || (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE) || (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16))
       return NFCGPU_EINVAL;
 
@@ -2830,6 +3688,8 @@ int nfcgpu_magnitude_fmt(nfcgpu_ctx *ctx, const void *iq, uint64_t n, float *out
 int nfcgpu_resample_radio(nfcgpu_ctx *ctx, const float *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, float *out, uint64_t outPitch,
                           uint32_t capacityPairs, uint32_t *counts, uint32_t location)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !in || !out || !counts || n < 25 || (inPitch & 3) || (outPitch & 7) || ((uintptr_t)out & 7) || inPitch < (uint64_t)n * 4 ||
        outPitch < (uint64_t)capacityPairs * 8 || (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE))
       return NFCGPU_EINVAL;
@@ -3003,6 +3863,8 @@ uint32_t nfcgpu_spectrum_frames(const nfcgpu_spectrum_params *p, uint32_t nPairs
 int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t nBuffers, uint32_t nPairs, const nfcgpu_spectrum_params *params,
                     float *out, uint64_t outPitch, uint32_t location)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -3147,6 +4009,27 @@ int nfcgpu_submit_uniform_fmt(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, c
 
    HIP_TRY(ctx, hipSetDevice(ctx->device));
 
+   /* A pending tail (run_windowed) is completed first - unless this submission may run its front under it: the very streams of
+    * the pending one, none of them with an initialisation pending or a changed sample rate. (What else stands in the way -
+    * another configuration, a clock near the wrap - is found further down, and the tail completed there.) */
+   if (ctx->tail)
+   {
+      bool candidate = ctx->pipeline && n != 0 && first == ctx->tail->items.front().slot && count == ctx->tail->items.size();
+
+      for (uint32_t i = first; candidate && i < first + count; i++)
+      {
+         const StreamInfo &si = ctx->streams[i];
+         candidate = si.open && si.initialized && !si.needInit && si.derivedRate != 0 && si.params.sample_rate == sampleRate;
+      }
+
+      if (!candidate)
+      {
+         int rc = settle_tail(ctx);
+         if (rc)
+            return rc;
+      }
+   }
+
    /* an empty buffer still stores a new sample rate and re-initialises the stream, like nfcgpu_submit (NfcDecoder.cpp:383-388) */
    for (uint32_t i = first; i < first + count; i++)
    {
@@ -3189,7 +4072,16 @@ int nfcgpu_submit_uniform_fmt(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, c
 
       release.slot = slot;
 
-      HIP_TRY(ctx, hipMemcpyAsync(slot->d, slot->h, devPitch * count, hipMemcpyHostToDevice, ctx->stream));
+      if (ctx->tail)
+      {
+         /* (the main stream is the pending tail's: the rows go up on the stream the front will run on, and whatever takes them
+          * from the main stream after all waits for that) */
+         HIP_TRY(ctx, hipMemcpyAsync(slot->d, slot->h, devPitch * count, hipMemcpyHostToDevice, ctx->front));
+         HIP_TRY(ctx, hipEventRecord(ctx->frontEvent, ctx->front));
+         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->frontEvent, 0));
+      }
+      else
+         HIP_TRY(ctx, hipMemcpyAsync(slot->d, slot->h, devPitch * count, hipMemcpyHostToDevice, ctx->stream));
       devBase = slot->d;
    }
 
@@ -3197,9 +4089,24 @@ int nfcgpu_submit_uniform_fmt(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, c
    if (rc)
       return rc;
 
+   /* (a submission of this kind may leave its tail pending: run_windowed) */
+   struct Deferring
+   {
+      nfcgpu_ctx *ctx;
+      ~Deferring() { ctx->deferOK = false; }
+   } deferring {ctx};
+   ctx->deferOK = true;
+
    rc = run_rows(ctx, first, count, devBase, devPitch, n, stride);
    if (rc)
       return rc;
+
+   /* the staging slot stays held until the pending tail is done: its kernels read the rows */
+   if (ctx->tail && release.slot)
+   {
+      ctx->tail->slot = release.slot;
+      release.slot = nullptr;
+   }
 
    /* host buffers are never retained past the call: they were copied into the staging slot */
    return NFCGPU_OK;
@@ -3207,6 +4114,8 @@ int nfcgpu_submit_uniform_fmt(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, c
 
 int nfcgpu_sync(nfcgpu_ctx *ctx)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -3357,6 +4266,8 @@ int nfcgpu_pending(nfcgpu_ctx *ctx, uint32_t id, uint32_t *count)
 
 int nfcgpu_sink_device_view(nfcgpu_ctx *ctx, const void **words, const void **cursor, uint64_t *capacity)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -3371,6 +4282,8 @@ int nfcgpu_sink_device_view(nfcgpu_ctx *ctx, const void **words, const void **cu
 
 int nfcgpu_sink_attach(nfcgpu_ctx *ctx, void *words, uint64_t capacityWords, void *ctl)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || (words && (!ctl || capacityWords < 4ull * NFC_FRAME_MAX_WORDS || capacityWords > 0xFFFFFFF0ull)))
       return NFCGPU_EINVAL;
 
@@ -3401,6 +4314,8 @@ int nfcgpu_sink_attach(nfcgpu_ctx *ctx, void *words, uint64_t capacityWords, voi
 
 int nfcgpu_sink_hold(nfcgpu_ctx *ctx, int hold)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -3410,6 +4325,8 @@ int nfcgpu_sink_hold(nfcgpu_ctx *ctx, int hold)
 
 int nfcgpu_sink_rewind(nfcgpu_ctx *ctx)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -3433,6 +4350,8 @@ int nfcgpu_comm_unique_id(void *id128)
 
 int nfcgpu_comm_init(nfcgpu_ctx *ctx, const void *id128, int rank, int nRanks)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !id128 || nRanks < 1 || rank < 0 || rank >= nRanks)
       return NFCGPU_EINVAL;
 
@@ -3466,6 +4385,8 @@ int nfcgpu_comm_init(nfcgpu_ctx *ctx, const void *id128, int rank, int nRanks)
 
 int nfcgpu_comm_destroy(nfcgpu_ctx *ctx)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -3494,6 +4415,8 @@ int nfcgpu_comm_destroy(nfcgpu_ctx *ctx)
  * stride = the largest count (the layout of rounds 1-2, kept under the old symbol) */
 static int gather_frames(nfcgpu_ctx *ctx, void *gathered, uint64_t capacityWords, uint32_t *countsHost, uint64_t *strideWords, bool packed)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !gathered || !countsHost || (!packed && !strideWords))
       return NFCGPU_EINVAL;
 
@@ -3586,6 +4509,8 @@ int nfcgpu_gather_frames(nfcgpu_ctx *ctx, void *gathered, uint64_t capacityWords
 
 int nfcgpu_read_bandwidth(nfcgpu_ctx *ctx, const void *ptr, uint64_t bytes, uint32_t repeats, double *gbps)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !ptr || bytes < 16 || !gbps || ((uintptr_t)ptr & 15))
       return NFCGPU_EINVAL;
 
@@ -3655,6 +4580,8 @@ void close_wave_spans(nfcgpu_ctx *ctx)
 
 int nfcgpu_stats_get(nfcgpu_ctx *ctx, nfcgpu_stats *stats)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !stats)
       return NFCGPU_EINVAL;
 
@@ -3664,6 +4591,8 @@ int nfcgpu_stats_get(nfcgpu_ctx *ctx, nfcgpu_stats *stats)
 
 int nfcgpu_stats_get_sized(nfcgpu_ctx *ctx, void *stats, uint32_t size)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || !stats)
       return NFCGPU_EINVAL;
 
@@ -3675,6 +4604,8 @@ int nfcgpu_stats_get_sized(nfcgpu_ctx *ctx, void *stats, uint32_t size)
 
 int nfcgpu_stats_reset(nfcgpu_ctx *ctx)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx)
       return NFCGPU_EINVAL;
 
@@ -3735,6 +4666,8 @@ const char *nfcgpu_last_error(nfcgpu_ctx *ctx)
  * way to preset its clock, so the product has none either. */
 int nfcgpu_test_set_clock(nfcgpu_ctx *ctx, uint32_t id, uint32_t clock)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || id >= ctx->maxStreams || !ctx->streams[id].open || !ctx->streams[id].initialized)
       return NFCGPU_ESTREAM;
    ctx->dStates[id].clock = clock;
@@ -3744,6 +4677,8 @@ int nfcgpu_test_set_clock(nfcgpu_ctx *ctx, uint32_t id, uint32_t clock)
 
 int nfcgpu_test_get_clock(nfcgpu_ctx *ctx, uint32_t id, uint32_t *device, uint32_t *mirror)
 {
+   SETTLE_FIRST(ctx);
+
    if (!ctx || id >= ctx->maxStreams || !device || !mirror)
       return NFCGPU_ESTREAM;
    *device = ctx->dStates[id].clock;
@@ -3795,6 +4730,9 @@ int run_rows(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, const uint8_t *dev
             continue;
          }
       }
+
+      if ((rc = settle_tail(ctx)))
+         return rc;
 
       NfcLaunch L = base_launch(ctx);
       L.works = nullptr;

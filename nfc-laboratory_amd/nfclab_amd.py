@@ -93,6 +93,9 @@ class Stats(ctypes.Structure):
         ("wave_launches", ctypes.c_uint64),
         ("planes_ms", ctypes.c_double),
         ("wave_busy_ms", ctypes.c_double),
+        ("pipelined_submissions", ctypes.c_uint64),
+        ("pipeline_refronts", ctypes.c_uint64),
+        ("pipeline_zeroed_edges", ctypes.c_uint64),
     ]
 
 
