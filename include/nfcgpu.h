@@ -274,6 +274,60 @@ uint32_t nfcgpu_spectrum_frames(const nfcgpu_spectrum_params *p, uint32_t n_pair
 int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_pairs,
                     const nfcgpu_spectrum_params *params, float *out, uint64_t out_pitch_bytes, uint32_t location);
 
+/* Recording: float samples to the 16-bit PCM of a capture file, with the receiver's levels, in one pass over the input - the
+ * per-sample loop of SignalStorageTask::writeRadio (SignalStorageTask.cpp:493-523, hw::RecordDevice::writeScaledSamples<short>,
+ * RecordDevice.cpp:313-348) and the level part of the magnitude loop of RadioDeviceTask::processQueue
+ * (RadioDeviceTask.cpp:547-680).
+ *
+ * Buffer b is n_samples * stride floats at in + b * in_pitch_bytes (`in` and in_pitch_bytes multiples of 4 * stride) and is
+ * written as n_samples * channels int16 at out + b * out_pitch_bytes (`out` and out_pitch_bytes multiples of 2 * channels and
+ * no more: a mono row may start on any 2-byte boundary; out_pitch_bytes at least the row; bytes of a pitch beyond the row are
+ * left alone). channels is 2 for stride 2 with NFCGPU_RECORD_SAME, else 1. NFCGPU_RECORD_MAGNITUDE (stride 2 only) records
+ * the magnitude the decoder's loader forms of an I/Q sample (nfcgpu_magnitude), so decoding the recording sees the
+ * magnitudes the decoder would have computed of the floats, quantised.
+ *
+ * A value v becomes t = v * 32768.0f (one fp32 product), q = t rounded toward zero; -32768 <= q <= 32767 is written as it is:
+ * for finite input in range that is the reference's static_cast<short>(v * 32768.0f), and k / 32768.0f gives k for every int16
+ * k (recording is a left inverse of NFCGPU_FMT_I16 input). One departure from the reference: outside that range its cast is
+ * undefined (on x86 it wraps: 1.0 is written as -32768); here values beyond the range and infinities saturate to 32767 or
+ * -32768 and NaN is written as 0, and every such value counts in `clipped`. Magnitudes of I/Q do exceed 1.0.
+ *
+ * levels (may be NULL: the reductions are skipped), one record per buffer, over the magnitudes m of the buffer (stride 2, both
+ * modes; stride 1: m is the input itself) - what RadioDeviceTask::processQueue derives per buffer:
+ *   power    sum(I*I + Q*Q) / n_samples (stride 1: sum(v*v) / n_samples), :623 / :646
+ *   average  the AGC average (:617-620 / :639, compared with 0.05 and 0.25 at :666-679): a = 0; for k = 0 ... ceil(n / 4) - 1:
+ *            a = a * (1 - 0.001f) + m[4 k] * 0.001f - the reference's recurrence over every fourth magnitude, restarted per
+ *            buffer; evaluated in parallel, within 2048 * 2^-24 relative of the exact value for non-negative m
+ *   peak     the largest m (stride 1: the largest value), NaNs ignored; 0 when there is none
+ *   clipped  PCM values written that were saturated or came from a NaN
+ * power is summed pairwise (no value passes through more than 60 additions). Results do not depend on the run, on the other
+ * buffers of the call or on where the rows lie. `location` applies to `in`, `out` and `levels`; the call returns when they are
+ * complete. n_samples == 0 or n_buffers == 0 is success and writes no PCM (levels of n_samples == 0 are all zero). */
+#define NFCGPU_RECORD_SAME 0u       /* stride 1 -> mono PCM; stride 2 -> two-channel I/Q PCM, interleaved */
+#define NFCGPU_RECORD_MAGNITUDE 1u  /* stride 2 only: magnitude (nfc_iq_magnitude) -> mono PCM */
+
+typedef struct nfcgpu_record_levels {   /* one per buffer, 16 bytes */
+   float power;
+   float average;
+   float peak;
+   uint32_t clipped;
+} nfcgpu_record_levels;
+
+int nfcgpu_record(nfcgpu_ctx *ctx, const float *in, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_samples,
+                  uint32_t stride, uint32_t mode, int16_t *out, uint64_t out_pitch_bytes,
+                  nfcgpu_record_levels *levels /* may be NULL */, uint32_t location);
+
+/* Capture files as hw::RecordDevice writes them (RecordDevice.cpp:493-546, structures :53-100), host only, no context and
+ * no device: a 92-byte header - RIFF / WAVE; "fmt " (16: PCM 1, channels, rate, byte rate, block align, 16 bits); "META" (40:
+ * "meta", epoch = stream_time, keys[8], the first `channels` taken from `keys`, NULL = zeros); "data" - then the samples,
+ * little-endian, interleaved. n_samples counts samples per channel. nfcgpu_wav_append adds samples to a file that starts with
+ * exactly this header (the channel count is the header's) and rewrites the RIFF and data sizes. NFCGPU_EIO: the file could not
+ * be opened or written. NFCGPU_EINVAL: channels 0 or more than 8, a NULL path, a file that would pass 4 GiB, appending to a
+ * file without that header. */
+int nfcgpu_wav_write(const char *path, const int16_t *pcm, uint64_t n_samples, uint32_t channels, uint32_t sample_rate,
+                     uint32_t stream_time, const int32_t *keys /* NULL = zeros, else `channels` values */);
+int nfcgpu_wav_append(const char *path, const int16_t *pcm, uint64_t n_samples);
+
 /* nextFrames(invalid buffer) (NfcDecoder.cpp:449-463): queues one carrier-state frame stamped with the stream's clock */
 int nfcgpu_flush(nfcgpu_ctx *ctx, uint32_t stream_id);
 /* waits for everything submitted, then moves the frames of the frame sink to the per-stream queues. poll / pending /

@@ -217,3 +217,150 @@ extern "C" int nfcgpu_trace_write_frames(const char *path, const nfcgpu_frame *f
 
    return write_gzip_stored(path, tar_of("frame.json", json));
 }
+
+/* ---- capture files: the header hw::RecordDevice writes (RecordDevice.cpp:493-546, structures :53-100) and the samples behind it ---- */
+
+namespace {
+
+const uint32_t kWavHeaderBytes = 92;
+
+void put16(uint8_t *at, uint32_t v)
+{
+   at[0] = (uint8_t)v;
+   at[1] = (uint8_t)(v >> 8);
+}
+
+void put32(uint8_t *at, uint32_t v)
+{
+   put16(at, v);
+   put16(at + 2, v >> 16);
+}
+
+uint32_t get16(const uint8_t *at)
+{
+   return (uint32_t)at[0] | ((uint32_t)at[1] << 8);
+}
+
+uint32_t get32(const uint8_t *at)
+{
+   return get16(at) | (get16(at + 2) << 16);
+}
+
+void wav_header(uint8_t *h, uint64_t fileBytes, uint32_t channels, uint32_t rate, uint32_t streamTime, const int32_t *keys)
+{
+   std::memset(h, 0, kWavHeaderBytes);
+   std::memcpy(h, "RIFF", 4);
+   put32(h + 4, (uint32_t)(fileBytes - 8));
+   std::memcpy(h + 8, "WAVE", 4);
+   std::memcpy(h + 12, "fmt ", 4);
+   put32(h + 16, 16);
+   put16(h + 20, 1);
+   put16(h + 22, channels);
+   put32(h + 24, rate);
+   put32(h + 28, channels * rate * 2);
+   put16(h + 32, channels * 2);
+   put16(h + 34, 16);
+   std::memcpy(h + 36, "META", 4);
+   put32(h + 40, 40);
+   std::memcpy(h + 44, "meta", 4);
+   put32(h + 48, streamTime);
+   for (uint32_t c = 0; keys && c < channels; c++)
+      put32(h + 52 + 4 * c, (uint32_t)keys[c]);
+   std::memcpy(h + 84, "data", 4);
+   put32(h + 88, (uint32_t)(fileBytes - kWavHeaderBytes));
+}
+
+/* the channel count of a header of exactly that shape, or 0 */
+uint32_t wav_header_channels(const uint8_t *h)
+{
+   if (std::memcmp(h, "RIFF", 4) || std::memcmp(h + 8, "WAVE", 4) || std::memcmp(h + 12, "fmt ", 4) || get32(h + 16) != 16 || get16(h + 20) != 1 ||
+       get16(h + 34) != 16 || std::memcmp(h + 36, "META", 4) || get32(h + 40) != 40 || std::memcmp(h + 44, "meta", 4) || std::memcmp(h + 84, "data", 4))
+      return 0;
+
+   const uint32_t channels = get16(h + 22);
+
+   if (channels == 0 || channels > 8 || get16(h + 32) != channels * 2)
+      return 0;
+
+   return channels;
+}
+
+bool wav_put_samples(std::FILE *f, const int16_t *pcm, uint64_t count)
+{
+   /* (little-endian samples, whatever the host) */
+   std::vector<uint8_t> block(65536);
+
+   while (count)
+   {
+      const size_t now = count < block.size() / 2 ? (size_t)count : block.size() / 2;
+      for (size_t i = 0; i < now; i++)
+         put16(block.data() + 2 * i, (uint16_t)pcm[i]);
+      if (std::fwrite(block.data(), 2, now, f) != now)
+         return false;
+      pcm += now;
+      count -= now;
+   }
+
+   return true;
+}
+
+}
+
+extern "C" int nfcgpu_wav_write(const char *path, const int16_t *pcm, uint64_t n_samples, uint32_t channels, uint32_t sample_rate, uint32_t stream_time,
+                                const int32_t *keys)
+{
+   if (!path || channels == 0 || channels > 8 || (n_samples && !pcm) || n_samples > (0xFFFFFFFFull - kWavHeaderBytes) / (2 * channels))
+      return NFCGPU_EINVAL;
+
+   std::FILE *f = std::fopen(path, "wb");
+   if (!f)
+      return NFCGPU_EIO;
+
+   uint8_t header[kWavHeaderBytes];
+   wav_header(header, kWavHeaderBytes + n_samples * channels * 2, channels, sample_rate, stream_time, keys);
+
+   bool ok = std::fwrite(header, 1, kWavHeaderBytes, f) == kWavHeaderBytes && wav_put_samples(f, pcm, n_samples * channels);
+   ok = (std::fclose(f) == 0) && ok;
+
+   return ok ? NFCGPU_OK : NFCGPU_EIO;
+}
+
+extern "C" int nfcgpu_wav_append(const char *path, const int16_t *pcm, uint64_t n_samples)
+{
+   if (!path || (n_samples && !pcm))
+      return NFCGPU_EINVAL;
+
+   std::FILE *f = std::fopen(path, "r+b");
+   if (!f)
+      return NFCGPU_EIO;
+
+   uint8_t header[kWavHeaderBytes];
+   const bool whole = std::fread(header, 1, kWavHeaderBytes, f) == kWavHeaderBytes;
+   const uint32_t channels = whole ? wav_header_channels(header) : 0;
+
+   if (!channels || std::fseek(f, 0, SEEK_END) != 0)
+   {
+      std::fclose(f);
+      return channels ? NFCGPU_EIO : NFCGPU_EINVAL;
+   }
+
+   const long at = std::ftell(f);
+   const uint64_t length = at < 0 ? 0 : (uint64_t)at;
+
+   if (length < kWavHeaderBytes || length != (uint64_t)get32(header + 88) + kWavHeaderBytes || length != (uint64_t)get32(header + 4) + 8 ||
+       n_samples > (0xFFFFFFFFull - length) / (2 * channels))
+   {
+      std::fclose(f);
+      return NFCGPU_EINVAL;
+   }
+
+   const uint64_t after = length + n_samples * channels * 2;
+   bool ok = wav_put_samples(f, pcm, n_samples * channels);
+
+   put32(header + 4, (uint32_t)(after - 8));
+   put32(header + 88, (uint32_t)(after - kWavHeaderBytes));
+   ok = ok && std::fseek(f, 0, SEEK_SET) == 0 && std::fwrite(header, 1, kWavHeaderBytes, f) == kWavHeaderBytes;
+   ok = (std::fclose(f) == 0) && ok;
+
+   return ok ? NFCGPU_OK : NFCGPU_EIO;
+}

@@ -28,6 +28,7 @@
 #include "nfc_scan_launch.h"
 #include "nfc_spectrum.hpp"
 #include "nfc_sample.hpp"
+#include "nfc_record.hpp"
 
 __global__ void nfc_demod_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
 __global__ void nfc_demod_exact_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
@@ -113,6 +114,127 @@ NFC_SPECTRUM_KERNEL(1024)
 NFC_SPECTRUM_KERNEL(2048)
 NFC_SPECTRUM_KERNEL(4096)
 #undef NFC_SPECTRUM_KERNEL
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+/* The test build's twins of the record kernels (nfc_record.hip): the quads, lanes, waves and segments of nfc_record.hpp as loops,
+ * every sum in the order the device takes it (the butterfly over a wave included). PCM goes out sample by sample: what is
+ * written does not depend on how the device packs its stores. */
+namespace {
+
+template <typename V, typename ADD>
+void record_twin_butterfly(V *lanes, ADD add)
+{
+   for (int off = 1; off < 64; off <<= 1)
+   {
+      V next[64];
+      for (int lane = 0; lane < 64; lane++)
+         next[lane] = add(lanes[lane], lanes[lane ^ off]);
+      for (int lane = 0; lane < 64; lane++)
+         lanes[lane] = next[lane];
+   }
+}
+
+template <int STRIDE, int MODE, bool LEVELS>
+void record_twin(const NfcRecordArgs &A)
+{
+   constexpr uint32_t EB = 2 * NfcRecordKind<STRIDE, MODE>::kChannels, IB = 4 * STRIDE;
+
+   for (uint64_t item = 0; item < A.total; item++)
+   {
+      const uint64_t b = item / A.nSegments;
+      const uint32_t s = (uint32_t)(item % A.nSegments);
+      const uint8_t *row = reinterpret_cast<const uint8_t *>(A.in) + b * A.inPitch;
+      uint8_t *orow = reinterpret_cast<uint8_t *>(A.out) + b * A.outPitch;
+      NfcRecordPartial waves[NfcRecordShape::kWaves];
+
+      for (uint32_t wave = 0; wave < NfcRecordShape::kWaves; wave++)
+      {
+         const uint32_t q0 = s * NfcRecordShape::kSegmentQuads + wave * NfcRecordShape::kWaveQuads;
+         NfcRecordPartial lanes[64];
+
+         for (uint32_t lane = 0; lane < 64; lane++)
+         {
+            NfcRecordPartial acc;
+            nfc_record_begin(acc);
+
+            for (uint32_t t = 0; t < NfcRecordShape::kIters && (uint64_t)q0 * 4 < A.n; t++)
+            {
+               const uint64_t i0 = (uint64_t)(q0 + t * 64 + lane) * 4;
+               const uint32_t valid = i0 < A.n ? (A.n - i0 < 4 ? (uint32_t)(A.n - i0) : 4u) : 0u;
+               uint32_t e[4] = {0, 0, 0, 0};
+
+               if (valid)
+                  nfc_record_quad<STRIDE, MODE, LEVELS>(reinterpret_cast<const float *>(row + i0 * IB), valid, e, acc, A.w);
+               else if (LEVELS)
+                  nfc_record_quad_none(acc, A.w);
+
+               for (uint32_t p = 0; p < valid; p++)
+                  std::memcpy(orow + (i0 + p) * EB, &e[p], EB); /* (little-endian host) */
+            }
+
+            nfc_record_lane_end(acc, lane, A.w);
+            lanes[lane] = acc;
+         }
+
+         if (LEVELS)
+            record_twin_butterfly(lanes, [](const NfcRecordPartial &x, const NfcRecordPartial &y) { return nfc_record_add(x, y); });
+         waves[wave] = lanes[0];
+      }
+
+      if (LEVELS)
+         A.partials[item] = nfc_record_segment(waves, A.w);
+   }
+}
+
+}
+
+void nfc_record_finish_kernel(NfcRecordArgs A)
+{
+   for (uint32_t b = 0; b < A.nBuffers; b++)
+   {
+      const NfcRecordPartial *seg = A.partials + (uint64_t)b * A.nSegments;
+      float peak = nfc_record_nan();
+      uint32_t clipped = 0;
+      std::vector<float> sums(A.nSegments);
+
+      for (uint32_t s = 0; s < A.nSegments; s++)
+      {
+         peak = nfc_record_max(peak, seg[s].peak);
+         clipped += seg[s].clipped;
+         sums[s] = seg[s].power;
+      }
+
+      /* groups of 64 until one value is left, short groups filled with zeros */
+      while (sums.size() > 1)
+      {
+         std::vector<float> next((sums.size() + 63) / 64);
+         for (size_t g = 0; g < next.size(); g++)
+         {
+            float lanes[64];
+            for (size_t lane = 0; lane < 64; lane++)
+               lanes[lane] = g * 64 + lane < sums.size() ? sums[g * 64 + lane] : 0.0f;
+            record_twin_butterfly(lanes, [](float x, float y) { return x + y; });
+            next[g] = lanes[0];
+         }
+         sums.swap(next);
+      }
+
+      A.levels[b] = nfc_record_levels(sums[0], nfc_record_chain_average(seg, A.nSegments, A.w), peak, clipped, A.n);
+   }
+}
+#define NFC_RECORD_KERNEL(name, STRIDE, MODE, LEVELS) \
+   void name(NfcRecordArgs A) { record_twin<STRIDE, MODE, LEVELS>(A); }
+#else
+#define NFC_RECORD_KERNEL(name, STRIDE, MODE, LEVELS) __global__ void name(NfcRecordArgs A);
+__global__ void nfc_record_finish_kernel(NfcRecordArgs A);
+#endif
+NFC_RECORD_KERNEL(nfc_record_kernel_mono, 1, NFC_RECORD_SAME, false)
+NFC_RECORD_KERNEL(nfc_record_kernel_mono_levels, 1, NFC_RECORD_SAME, true)
+NFC_RECORD_KERNEL(nfc_record_kernel_iq, 2, NFC_RECORD_SAME, false)
+NFC_RECORD_KERNEL(nfc_record_kernel_iq_levels, 2, NFC_RECORD_SAME, true)
+NFC_RECORD_KERNEL(nfc_record_kernel_magnitude, 2, NFC_RECORD_MAGNITUDE, false)
+NFC_RECORD_KERNEL(nfc_record_kernel_magnitude_levels, 2, NFC_RECORD_MAGNITUDE, true)
+#undef NFC_RECORD_KERNEL
 
 /* ---- helper kernels of pipelined submissions (run_windowed): a thread per stream of the submission ----
  * The front of a submission (scan, seam rounds, planes) reads of a stream's slot the front-end state its first chunk starts from:
@@ -494,6 +616,10 @@ struct nfcgpu_ctx
       float *d = nullptr; /* `length` window factors, then `length` twiddles (float2) */
    };
    std::vector<SpectrumTables> spectrumTables;
+
+   /* nfcgpu_record: one partial per segment of every buffer of a call (device), grown on demand, kept */
+   void *recordPartials = nullptr;
+   size_t recordPartialsBytes = 0;
 };
 
 namespace {
@@ -3162,6 +3288,8 @@ int nfcgpu_shutdown(nfcgpu_ctx *ctx)
    (void)hipFree(ctx->dConfigs);
    for (nfcgpu_ctx::SpectrumTables &t: ctx->spectrumTables)
       (void)hipFree(t.d);
+   if (ctx->recordPartials)
+      (void)hipFree(ctx->recordPartials);
    for (nfcgpu_ctx::StageSlot &slot: ctx->stage)
    {
       if (slot.d)
@@ -3962,6 +4090,196 @@ int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t
 
    if (err != hipSuccess)
       return fail(ctx, NFCGPU_EHIP, "spectrum", err);
+
+   return NFCGPU_OK;
+}
+
+/* ---- nfcgpu_record: the recording pass (SignalStorageTask.cpp:493-523, RecordDevice.cpp:313-348) and the levels of
+ * RadioDeviceTask::processQueue (RadioDeviceTask.cpp:547-680) in one read of every buffer ---- */
+
+static_assert(sizeof(nfcgpu_record_levels) == sizeof(NfcRecordPartial) && sizeof(NfcRecordPartial) == 16, "a levels record is 16 bytes");
+
+/* the powers of w0 = 1 - 0.001f the kernels weight with, in double, rounded once */
+static void record_weights(NfcRecordWeights &w, uint32_t n)
+{
+   const float w1 = 0.001f, w0 = 1.0f - w1;
+   const uint64_t quads = ((uint64_t)n + 3) / 4;
+   const uint64_t lastQuads = quads - (quads - 1) / NfcRecordShape::kSegmentQuads * NfcRecordShape::kSegmentQuads;
+
+   w.w1 = w1;
+   w.w64 = (float)std::pow((double)w0, 64.0);
+   w.segment = (float)std::pow((double)w0, (double)NfcRecordShape::kSegmentQuads);
+   w.last = (float)std::pow((double)w0, (double)lastQuads);
+   w.unpad = (float)std::pow((double)w0, -(double)(NfcRecordShape::kSegmentQuads - lastQuads));
+   for (uint32_t i = 0; i < NfcRecordShape::kWaves; i++)
+      w.wave[i] = (float)std::pow((double)w0, (double)(NfcRecordShape::kWaveQuads * (NfcRecordShape::kWaves - 1 - i)));
+   for (uint32_t i = 0; i < 64; i++)
+      w.lane[i] = (float)std::pow((double)w0, (double)(63 - i));
+}
+
+int nfcgpu_record(nfcgpu_ctx *ctx, const float *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, uint32_t stride, uint32_t mode, int16_t *out,
+                  uint64_t outPitch, nfcgpu_record_levels *levels, uint32_t location)
+{
+   SETTLE_FIRST(ctx);
+
+   if (!ctx)
+      return NFCGPU_EINVAL;
+   if (stride != 1 && stride != 2)
+      return fail(ctx, NFCGPU_EINVAL, "record: stride is neither 1 nor 2");
+   if (mode != NFCGPU_RECORD_SAME && mode != NFCGPU_RECORD_MAGNITUDE)
+      return fail(ctx, NFCGPU_EINVAL, "record: unknown mode");
+   if (mode == NFCGPU_RECORD_MAGNITUDE && stride != 2)
+      return fail(ctx, NFCGPU_EINVAL, "record: mode NFCGPU_RECORD_MAGNITUDE needs stride 2");
+   if (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE)
+      return fail(ctx, NFCGPU_EINVAL, "record: unknown location");
+
+   const uint32_t channels = (stride == 2 && mode == NFCGPU_RECORD_SAME) ? 2 : 1;
+   const uint64_t inSample = 4 * stride, outSample = 2 * channels;
+   const uint64_t rowBytes = (uint64_t)n * outSample;
+
+   if (!in || ((uintptr_t)in % inSample))
+      return fail(ctx, NFCGPU_EINVAL, "record: in is NULL or not aligned to a sample (4 * stride bytes)");
+   if (!out || ((uintptr_t)out % outSample))
+      return fail(ctx, NFCGPU_EINVAL, "record: out is NULL or not aligned to a PCM sample (2 * channels bytes)");
+   if (levels && ((uintptr_t)levels & 3))
+      return fail(ctx, NFCGPU_EINVAL, "record: levels is not 4-byte aligned");
+   if (inPitch % inSample)
+      return fail(ctx, NFCGPU_EINVAL, "record: in_pitch_bytes is not a multiple of a sample (4 * stride bytes)");
+   if ((outPitch % outSample) || outPitch < rowBytes)
+      return fail(ctx, NFCGPU_EINVAL, "record: out_pitch_bytes is not a multiple of a PCM sample (2 * channels bytes) or smaller than a row");
+   if (nBuffers == 0)
+      return NFCGPU_OK;
+
+   HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+   const size_t levelBytes = levels ? (size_t)nBuffers * sizeof(nfcgpu_record_levels) : 0;
+
+   if (n == 0)
+   {
+      if (levels && location == NFCGPU_LOC_HOST)
+         std::memset(levels, 0, levelBytes);
+      else if (levels)
+      {
+         HIP_TRY(ctx, hipMemsetAsync(levels, 0, levelBytes, ctx->stream));
+         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      }
+      return NFCGPU_OK;
+   }
+
+   NfcRecordArgs A;
+   std::memset(&A, 0, sizeof(A));
+
+   A.nSegments = (uint32_t)(((uint64_t)n + NfcRecordShape::kSegmentSamples - 1) / NfcRecordShape::kSegmentSamples);
+   A.total = (uint64_t)nBuffers * A.nSegments;
+   A.n = n;
+   A.nBuffers = nBuffers;
+   A.inPitch = inPitch;
+   A.outPitch = outPitch;
+   record_weights(A.w, n);
+
+   if (levels)
+   {
+      const size_t need = (size_t)A.total * sizeof(NfcRecordPartial);
+
+      if (need > ctx->recordPartialsBytes)
+      {
+         if (ctx->recordPartials)
+            (void)hipFree(ctx->recordPartials);
+         ctx->recordPartials = nullptr;
+         ctx->recordPartialsBytes = 0;
+         if (hipMalloc(&ctx->recordPartials, need) != hipSuccess)
+            return fail(ctx, NFCGPU_ENOMEM, "record: scratch for the levels could not be allocated");
+         ctx->recordPartialsBytes = need;
+      }
+
+      A.partials = (NfcRecordPartial *)ctx->recordPartials;
+   }
+
+   uint8_t *scratch = nullptr;
+   /* what the buffers span: the pitch between them, the data of the last one */
+   const size_t inBytes = (size_t)inPitch * (nBuffers - 1) + (size_t)n * inSample, outBytes = (size_t)outPitch * (nBuffers - 1) + (size_t)rowBytes;
+   /* (the copy of `out` lies as `out` does within 16 bytes, so the kernel packs its stores as it would in place) */
+   const size_t inRoom = (inBytes + 15) & ~(size_t)15, outShift = (uintptr_t)out & 15, outRoom = (outShift + outBytes + 15) & ~(size_t)15;
+
+   A.in = in;
+   A.out = out;
+   A.levels = (NfcRecordPartial *)levels;
+
+   if (location == NFCGPU_LOC_HOST)
+   {
+      /* one temporary device block: input, output, levels (this entry point is not on the streaming path) */
+      if (hipMalloc((void **)&scratch, inRoom + outRoom + levelBytes) != hipSuccess)
+         return fail(ctx, NFCGPU_ENOMEM, "record: scratch allocation failed");
+
+      hipError_t err = hipMemcpy(scratch, in, inBytes, hipMemcpyHostToDevice);
+      if (err != hipSuccess)
+      {
+         (void)hipFree(scratch);
+         return fail(ctx, NFCGPU_EHIP, "hipMemcpy(H2D record input)", err);
+      }
+
+      A.in = (const float *)scratch;
+      A.out = (int16_t *)(scratch + inRoom + outShift);
+      A.levels = levels ? (NfcRecordPartial *)(scratch + inRoom + outRoom) : nullptr;
+   }
+
+   /* one workgroup per segment; beyond 2^20 workgroups each takes several */
+   const dim3 grid((uint32_t)(A.total < (1u << 20) ? A.total : (1u << 20))), block(NfcRecordShape::kThreads);
+
+   if (stride == 1)
+   {
+      if (levels)
+         hipLaunchKernelGGL(nfc_record_kernel_mono_levels, grid, block, 0, ctx->stream, A);
+      else
+         hipLaunchKernelGGL(nfc_record_kernel_mono, grid, block, 0, ctx->stream, A);
+   }
+   else if (mode == NFCGPU_RECORD_SAME)
+   {
+      if (levels)
+         hipLaunchKernelGGL(nfc_record_kernel_iq_levels, grid, block, 0, ctx->stream, A);
+      else
+         hipLaunchKernelGGL(nfc_record_kernel_iq, grid, block, 0, ctx->stream, A);
+   }
+   else
+   {
+      if (levels)
+         hipLaunchKernelGGL(nfc_record_kernel_magnitude_levels, grid, block, 0, ctx->stream, A);
+      else
+         hipLaunchKernelGGL(nfc_record_kernel_magnitude, grid, block, 0, ctx->stream, A);
+   }
+
+   hipError_t err = hipGetLastError();
+
+   if (err == hipSuccess && levels)
+   {
+      hipLaunchKernelGGL(nfc_record_finish_kernel, dim3(nBuffers < 65536u ? nBuffers : 65536u), dim3(64), 0, ctx->stream, A);
+      err = hipGetLastError();
+   }
+
+   if (err == hipSuccess)
+      err = hipStreamSynchronize(ctx->stream);
+
+   if (err == hipSuccess && location == NFCGPU_LOC_HOST)
+   {
+      /* the PCM of every buffer goes to the caller's rows; what lies between the rows is the caller's */
+      std::vector<uint8_t> back(outBytes + levelBytes);
+      err = hipMemcpy(back.data(), A.out, outBytes, hipMemcpyDeviceToHost);
+      if (err == hipSuccess && levels)
+         err = hipMemcpy(back.data() + outBytes, A.levels, levelBytes, hipMemcpyDeviceToHost);
+      if (err == hipSuccess)
+      {
+         for (uint32_t b = 0; b < nBuffers; b++)
+            std::memcpy((uint8_t *)out + (size_t)b * outPitch, back.data() + (size_t)b * outPitch, (size_t)rowBytes);
+         if (levels)
+            std::memcpy(levels, back.data() + outBytes, levelBytes);
+      }
+   }
+
+   if (scratch)
+      (void)hipFree(scratch);
+
+   if (err != hipSuccess)
+      return fail(ctx, NFCGPU_EHIP, "record", err);
 
    return NFCGPU_OK;
 }

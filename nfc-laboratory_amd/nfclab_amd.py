@@ -18,6 +18,12 @@ LOC_HOST, LOC_DEVICE = 0, 1
 # value = v / 32768, converted by the kernels as they load
 FMT_F32, FMT_I16 = 0, 1
 
+# what nfcgpu_record writes (NFCGPU_RECORD_*): the input as it is (mono PCM, or two-channel I/Q PCM for stride 2), or the magnitude
+# of stride-2 I/Q as mono PCM
+RECORD_SAME, RECORD_MAGNITUDE = 0, 1
+# one nfcgpu_record_levels per buffer
+LEVELS_DTYPE = np.dtype([("power", np.float32), ("average", np.float32), ("peak", np.float32), ("clipped", np.uint32)])
+
 FRAME_CARRIER_OFF, FRAME_CARRIER_ON, FRAME_POLL, FRAME_LISTEN = 0x100, 0x101, 0x102, 0x103
 
 
@@ -161,6 +167,9 @@ def load_library(path=LIB_PATH):
     lib.nfcgpu_spectrum_frames.argtypes = [P(SpectrumParams), u32]
     lib.nfcgpu_spectrum_frames.restype = u32
     lib.nfcgpu_spectrum.argtypes = [vp, vp, u64, u32, u32, P(SpectrumParams), vp, u64, u32]
+    lib.nfcgpu_record.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, u64, vp, u32]
+    lib.nfcgpu_wav_write.argtypes = [ctypes.c_char_p, vp, u64, u32, u32, u32, vp]
+    lib.nfcgpu_wav_append.argtypes = [ctypes.c_char_p, vp, u64]
     lib.nfcgpu_flush.argtypes = [vp, u32]
     lib.nfcgpu_sync.argtypes = [vp]
     lib.nfcgpu_poll.argtypes = [vp, u32, P(Frame), u32, P(u32)]
@@ -198,6 +207,33 @@ def default_params(sample_rate=0, tech_mask=0xF):
     p.sample_rate = sample_rate
     p.tech_mask = tech_mask
     return p
+
+
+def _wav_check(rc):
+    if rc != 0:
+        raise NfcGpuError(rc, load_library().nfcgpu_strerror(rc).decode())
+
+
+def wav_write(path, pcm, sample_rate, channels=1, stream_time=0, keys=None):
+    """A capture file as the reference's hw::RecordDevice writes it (nfcgpu_wav_write): int16 samples, interleaved for
+    channels > 1. No context and no device."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+    assert channels and pcm.size % channels == 0
+    k = None if keys is None else np.ascontiguousarray(keys, dtype=np.int32)
+    assert k is None or k.size == channels
+    _wav_check(load_library().nfcgpu_wav_write(os.fsencode(path), pcm.ctypes.data, pcm.size // channels, channels, sample_rate, stream_time,
+                                               None if k is None else k.ctypes.data))
+
+
+def wav_append(path, pcm):
+    """More samples behind those of a file wav_write made (nfcgpu_wav_append); the channel count is the file's."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+    with open(path, "rb") as f:
+        header = f.read(24)
+    channels = int.from_bytes(header[22:24], "little") if len(header) == 24 else 0
+    if channels == 0 or pcm.size % channels:
+        raise NfcGpuError(-1, "not a capture file, or samples that do not fill its channels")
+    _wav_check(load_library().nfcgpu_wav_append(os.fsencode(path), pcm.ctypes.data, pcm.size // channels))
 
 
 class NfcGpu:
@@ -337,6 +373,25 @@ class NfcGpu:
         self._check(self.lib.nfcgpu_spectrum(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_pairs, ctypes.byref(p), out_ptr,
                                              out_pitch_bytes, LOC_DEVICE))
         return self.lib.nfcgpu_spectrum_frames(ctypes.byref(p), n_pairs)
+
+    def record(self, buffers, stride=1, mode=RECORD_SAME, levels=True):
+        """16-bit PCM of a float32 array [n_buffers, n * stride] (host memory) as a capture file holds it, and the levels of
+        every buffer (nfcgpu_record): (int16 [n_buffers, n * channels], LEVELS_DTYPE [n_buffers] or None)."""
+        buffers = np.ascontiguousarray(buffers, dtype=np.float32)
+        nb, width = buffers.shape
+        assert width % stride == 0
+        n = width // stride
+        channels = 2 if stride == 2 and mode == RECORD_SAME else 1
+        out = np.zeros((nb, n * channels), dtype=np.int16)
+        lv = np.zeros(nb, dtype=LEVELS_DTYPE) if levels else None
+        self._check(self.lib.nfcgpu_record(self.ctx, buffers.ctypes.data, width * 4, nb, n, stride, mode, out.ctypes.data, n * channels * 2,
+                                           lv.ctypes.data if levels else None, LOC_HOST))
+        return out, lv
+
+    def record_device(self, in_ptr, in_pitch_bytes, n_buffers, n_samples, out_ptr, out_pitch_bytes, stride=1, mode=RECORD_SAME, levels_ptr=None):
+        """Same with device pointers (samples, PCM and levels resident in HBM); levels_ptr None skips the levels."""
+        self._check(self.lib.nfcgpu_record(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, stride, mode, out_ptr, out_pitch_bytes,
+                                           levels_ptr, LOC_DEVICE))
 
     def flush(self, stream):
         self._check(self.lib.nfcgpu_flush(self.ctx, stream))
