@@ -1801,116 +1801,153 @@ void swap_front_sets(nfcgpu_ctx *ctx)
       std::swap(*mine[i], ctx->otherSet[i]);
 }
 
-/* One submission of `items` (all of configuration `config`, `stride` floats per sample, data resident on the device)
- * through scan -> windows -> windowed decode -> chain -> finish; streams the path cannot vouch for (samples off the
- * int16 grid, a seam that did not verify, no settled chain) are then decoded sequentially from their untouched state.
- *
- * It has a front - tables, scan, seam rounds, planes, tile flags: a function of the samples and of the front-end state the
- * streams start from - and a back: windows, decode passes, chain, finish. The back's own end (WindowedTail) may stay pending
- * when the call returns; a submission that continues the same streams then runs its front under it, on ctx->front, from the
- * shadow states the pending submission's back has left for it (nfc_shadow_kernel), and once the tail is done has the shadows
- * compared with what the finish really wrote: a front that started from anything else is walked again from the true state. */
-int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedItem> &items, uint32_t stride)
+/* A time-parallel submission from its plan to the hand-off to its tail: what the stages below read and write. It lives on the
+ * stack of run_windowed; the stages are free functions in the order they run, and what is left of the submission afterwards is
+ * copied into its WindowedTail. */
+struct WindowedSubmission
 {
-   const auto entered = std::chrono::steady_clock::now(); /* (the stage log counts the host's tables from here) */
-   const uint32_t nJobs = (uint32_t)items.size();
-   const NfcConfig &cfg = ctx->configs[config];
-   int rc;
+   /* what was submitted */
+   const uint32_t config, stride;
+   const std::vector<WindowedItem> &items;
+   const NfcConfig &cfg;
+   const uint32_t nJobs;
 
-   /* NFCGPU_WINDOW_DEBUG: where the time of a submission goes (synchronises at every mark) */
-   const bool debugStages = std::getenv("NFCGPU_WINDOW_DEBUG") != nullptr;
+   /* NFCGPU_WINDOW_DEBUG: where the time of a submission goes (synchronises at every mark); its value is how much else is shown */
+   const bool debugStages;
+   const int debugLevel;
+   std::chrono::steady_clock::time_point stageBegan; /* (the stage log counts the host's tables from the call's entry) */
 
-   bool under = false; /* the front runs under the pending tail */
+   bool under = false;  /* the front runs under the pending tail */
+   bool routed = false; /* a stage has handed the whole submission to somebody else (blocks, quarters, the sequential kernels): its result is the call's */
 
-   if (ctx->tail)
-   {
-      under = !debugStages && may_overlap(ctx, config, items);
-
-      if (!under && (rc = settle_tail(ctx)))
-         return rc;
-   }
-
-   if (debugStages && ctx->pipeline && !ctx->inBlocks)
-      std::fprintf(stderr, "[nfcgpu] the stage log is of unpipelined submissions: with NFCGPU_WINDOW_DEBUG set every submission is complete when its call returns\n");
-
-   /* A work buffer the device cannot give (NFCGPU_ENOMEM from grow()) is not the end of a submission as long as nothing of the
-    * streams has been touched - which holds up to the finish: the scan and the lanes only read the streams' state. The
-    * submission is then decoded a quarter of its length at a time (a quarter of every work buffer), and if that does not fit
-    * either by the sequential kernels, which need none. Any other error is the caller's. */
-   auto withoutTheMemory = [&](int code) -> int {
-      if (code != NFCGPU_ENOMEM)
-         return code;
-
-      (void)hipGetLastError();
-
-      uint32_t longest = 0;
-      for (const WindowedItem &it: items)
-         longest = it.count > longest ? it.count : longest;
-
-      const uint32_t quarter = longest / 4u / NFC_SCAN_POINT * NFC_SCAN_POINT;
-
-      if (!ctx->inBlocks && quarter >= 65536u && quarter >= ctx->windowedMinSamples)
-         return run_in_blocks(ctx, config, items, stride, quarter);
-
-      ctx->stats.fallback_streams += nJobs;
-      return launch_sequential(ctx, config, items, stride);
-   };
-
+   /* the plan: plan_scan_params, plan_tables */
    NfcScanParams sp;
+   std::vector<NfcScanJob> jobs; /* (uploaded by the front; a small submission's are read back in its first seam round, counts of busy tiles filled in) */
+   std::vector<NfcScanChunk> chunks;
+   uint32_t nChunks = 0, tiles = 0, points = 0, tilesMost = 0, tilesGridY = 0;
+   uint64_t totalSamples = 0;
+   uint32_t finalLaneSlot = 0, firstWindowSlot = 0;
+
+   /* what the kernels are given: fill_scan_args, then the front (planes, planesStale, states) and the back (lanes, save area) */
+   NfcScanArgs A;
+   const NfcConfig *dCfg = nullptr;
+   uint32_t *counters = nullptr;
+
+   /* the back */
+   uint32_t nWindows = 0;
+   bool shadows = false; /* shadow states have been asked for: the next submission may run its front under this one's tail */
+};
+
+/* the stage log: the stream is waited for and the time since the mark before printed */
+void mark_stage(nfcgpu_ctx *ctx, WindowedSubmission &W, const char *what)
+{
+   if (!W.debugStages)
+      return;
+   (void)hipStreamSynchronize(ctx->stream);
+   const auto now = std::chrono::steady_clock::now();
+   std::fprintf(stderr, "[nfcgpu] windowed stage %-10s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - W.stageBegan).count());
+   W.stageBegan = now;
+}
+
+/* A work buffer the device cannot give (NFCGPU_ENOMEM from grow()) is not the end of a submission as long as nothing of the
+ * streams has been touched - which holds up to the finish: the scan and the lanes only read the streams' state. The
+ * submission is then decoded a quarter of its length at a time (a quarter of every work buffer), and if that does not fit
+ * either by the sequential kernels, which need none. Any other error is the caller's.
+ *
+ * Reads the items; writes W.routed. Queues nothing itself: the submission is whoever it is handed to's. */
+int without_the_memory(nfcgpu_ctx *ctx, WindowedSubmission &W, int code)
+{
+   W.routed = true;
+
+   if (code != NFCGPU_ENOMEM)
+      return code;
+
+   (void)hipGetLastError();
+
+   uint32_t longest = 0;
+   for (const WindowedItem &it: W.items)
+      longest = it.count > longest ? it.count : longest;
+
+   const uint32_t quarter = longest / 4u / NFC_SCAN_POINT * NFC_SCAN_POINT;
+
+   if (!ctx->inBlocks && quarter >= 65536u && quarter >= ctx->windowedMinSamples)
+      return run_in_blocks(ctx, W.config, W.items, W.stride, quarter);
+
+   ctx->stats.fallback_streams += W.nJobs;
+   return launch_sequential(ctx, W.config, W.items, W.stride);
+}
+
+/* ---- the plan: host work alone, nothing is queued ---- */
+
+/* The scan parameters (W.sp): thresholds from the configuration, chunk and warm-up lengths from the context's settings and the
+ * submission's size. Reads W.cfg and the items. */
+void plan_scan_params(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   const NfcConfig &cfg = W.cfg;
+   const std::vector<WindowedItem> &items = W.items;
+   NfcScanParams &sp = W.sp;
+
+   float corr = 3.0e38f;
+   if (cfg.enabled & 1u) corr = cfg.corrThreshold[0] < corr ? cfg.corrThreshold[0] : corr;
+   if (cfg.enabled & 4u) corr = cfg.corrThreshold[2] < corr ? cfg.corrThreshold[2] : corr;
+   if (cfg.enabled & 8u) corr = cfg.corrThreshold[3] < corr ? cfg.corrThreshold[3] : corr;
+   sp.rangeK = corr < 1.0e30f ? 0.49f * corr : 3.0e38f;
+   sp.edgeK = (cfg.enabled & 2u) ? 0.99f * cfg.minDepth[1] : 3.0e38f;
+   float deep = 1.0f;
+   for (int t = 0; t < 4; t++)
+      if ((cfg.enabled >> t) & 1u)
+         deep = cfg.maxDepth[t] < deep ? cfg.maxDepth[t] : deep;
+   sp.deepK = 0.98f * deep;
+   sp.chunkSamples = ctx->scanChunk;
+   sp.warmSamples = ctx->scanWarm;
+   sp.soloSamples = ctx->soloSamples;
+   sp.offGridAlone = 1u;
+
+   /* Every chunk pays the warm-up again, so chunks should be as long as the machine allows: one lane per chunk, and
+    * 131072 lanes (256 CUs x 4 SIMDs x 2 waves of the scan kernel's 204 registers x 64) are resident at a time.
+    * Measured on 4096 streams x 2^20 idle samples: 8192 -> 1347, 16384 -> 1673, 32768 -> 1906 GB/s. */
+   if (!ctx->scanChunkFixed)
    {
-      float corr = 3.0e38f;
-      if (cfg.enabled & 1u) corr = cfg.corrThreshold[0] < corr ? cfg.corrThreshold[0] : corr;
-      if (cfg.enabled & 4u) corr = cfg.corrThreshold[2] < corr ? cfg.corrThreshold[2] : corr;
-      if (cfg.enabled & 8u) corr = cfg.corrThreshold[3] < corr ? cfg.corrThreshold[3] : corr;
-      sp.rangeK = corr < 1.0e30f ? 0.49f * corr : 3.0e38f;
-      sp.edgeK = (cfg.enabled & 2u) ? 0.99f * cfg.minDepth[1] : 3.0e38f;
-      float deep = 1.0f;
-      for (int t = 0; t < 4; t++)
-         if ((cfg.enabled >> t) & 1u)
-            deep = cfg.maxDepth[t] < deep ? cfg.maxDepth[t] : deep;
-      sp.deepK = 0.98f * deep;
-      sp.chunkSamples = ctx->scanChunk;
-      sp.warmSamples = ctx->scanWarm;
-      sp.soloSamples = ctx->soloSamples;
-      sp.offGridAlone = 1u;
+      uint64_t total = 0;
+      for (const WindowedItem &it: items)
+         total += it.count;
 
-      /* Every chunk pays the warm-up again, so chunks should be as long as the machine allows: one lane per chunk, and
-       * 131072 lanes (256 CUs x 4 SIMDs x 2 waves of the scan kernel's 204 registers x 64) are resident at a time.
-       * Measured on 4096 streams x 2^20 idle samples: 8192 -> 1347, 16384 -> 1673, 32768 -> 1906 GB/s. */
-      if (!ctx->scanChunkFixed)
+      /* (round 4: a sixteenth of that is enough lanes. What a submission of 2^29 samples - 512 busy streams, an eighth of
+       * config 5 - pays for are the rounds of second walks, a launch and a trip to the host each, and a chain of chunks that
+       * inherit a wrong envelope from each other is as many rounds as it has chunks: 27 rounds of 4096-sample chunks, 8 of
+       * 32768. 512 / 1024 dense streams x 2^20: 352 -> 321 ms per step.) */
+      uint64_t chunk = total / ctx->scanLanes / NFC_SCAN_POINT * NFC_SCAN_POINT;
+      if (chunk > 32768u)
+         chunk = 32768u;
+      if (chunk > sp.chunkSamples)
+         sp.chunkSamples = (uint32_t)chunk;
+
+      /* A small submission is one a caller waits for (a capture, a receiver's block): what counts is the time of the
+       * longest walk, chunk + warm-up at ~0.4 us per sample and lane. Shorter chunks and a warm-up that just covers the
+       * slowest recurrence (the average: 0.995^k) cut it; seams that do not verify cost a short second walk now. */
+      if (total <= (4u << 20))
       {
-         uint64_t total = 0;
-         for (const WindowedItem &it: items)
-            total += it.count;
-
-         /* (round 4: a sixteenth of that is enough lanes. What a submission of 2^29 samples - 512 busy streams, an eighth of
-          * config 5 - pays for are the rounds of second walks, a launch and a trip to the host each, and a chain of chunks that
-          * inherit a wrong envelope from each other is as many rounds as it has chunks: 27 rounds of 4096-sample chunks, 8 of
-          * 32768. 512 / 1024 dense streams x 2^20: 352 -> 321 ms per step.) */
-         uint64_t chunk = total / ctx->scanLanes / NFC_SCAN_POINT * NFC_SCAN_POINT;
-         if (chunk > 32768u)
-            chunk = 32768u;
-         if (chunk > sp.chunkSamples)
-            sp.chunkSamples = (uint32_t)chunk;
-
-         /* A small submission is one a caller waits for (a capture, a receiver's block): what counts is the time of the
-          * longest walk, chunk + warm-up at ~0.4 us per sample and lane. Shorter chunks and a warm-up that just covers the
-          * slowest recurrence (the average: 0.995^k) cut it; seams that do not verify cost a short second walk now. */
-         if (total <= (4u << 20))
-         {
-            if (sp.chunkSamples > 4096u)
-               sp.chunkSamples = 4096u;
-            if (sp.warmSamples > 3072u)
-               sp.warmSamples = 3072u;
-         }
+         if (sp.chunkSamples > 4096u)
+            sp.chunkSamples = 4096u;
+         if (sp.warmSamples > 3072u)
+            sp.warmSamples = 3072u;
       }
    }
+}
 
-   /* job and chunk tables */
-   std::vector<NfcScanJob> jobs(nJobs);
-   std::vector<NfcScanChunk> chunks;
-   uint32_t tiles = 0, points = 0, tilesMost = 0;
-   uint64_t totalSamples = 0;
+/* Job and chunk tables (W.jobs, W.chunks) with the lane cut, and the sizes everything after them is dimensioned by: tiles,
+ * points, chunks, samples, the lane slots, the y extent of a grid over tiles. Reads the items and W.sp. */
+void plan_tables(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   const std::vector<WindowedItem> &items = W.items;
+   const NfcScanParams &sp = W.sp;
+   const uint32_t nJobs = W.nJobs;
+   std::vector<NfcScanJob> &jobs = W.jobs;
+   std::vector<NfcScanChunk> &chunks = W.chunks;
+   uint32_t &tiles = W.tiles, &points = W.points, &tilesMost = W.tilesMost;
+   uint64_t &totalSamples = W.totalSamples;
+
+   jobs.resize(nJobs);
 
    for (uint32_t j = 0; j < nJobs; j++)
    {
@@ -1944,84 +1981,114 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
          job.cut = (uint32_t)cut;
    }
 
-   const uint32_t nChunks = (uint32_t)chunks.size();
-   const uint32_t finalLaneSlot = (nJobs + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
-   const uint32_t firstWindowSlot = 2 * finalLaneSlot;
+   W.nChunks = (uint32_t)chunks.size();
+   W.finalLaneSlot = (nJobs + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
+   W.firstWindowSlot = 2 * W.finalLaneSlot;
 
-   /* The buffers the front writes and the tail still reads. Under a pending tail the front takes the second set of them (grown
-    * here to everything the front may ask for, so that nothing is grown while it runs); a second set the device cannot give
-    * means no overlap for this context - never the fallbacks of withoutTheMemory. */
-   auto growFront = [&](bool all) -> int {
-      int r;
-      if ((r = grow(ctx, ctx->wJobs, sizeof(NfcScanJob) * nJobs)) || (r = grow(ctx, ctx->wChunks, sizeof(NfcScanChunk) * nChunks)) ||
-          (r = grow(ctx, ctx->wPoints, sizeof(NfcScanPoint) * (size_t)points)) || (r = grow(ctx, ctx->wSeams, sizeof(NfcScanSeam) * nChunks)) ||
-          (r = grow(ctx, ctx->wChunkEdge, 4 * (size_t)nChunks)) || (r = grow(ctx, ctx->wTiles, 4 * (size_t)tiles)) ||
-          (r = grow(ctx, ctx->wTileStats, sizeof(NfcScanTile) * (size_t)tiles)) ||
-          (r = grow(ctx, ctx->wCounters, 256)) || (r = grow(ctx, ctx->wRepairs, sizeof(NfcScanChunk) * nChunks)) ||
-          (r = grow(ctx, ctx->wRepairsEnv, sizeof(NfcScanChunk) * nChunks)))
-         return r;
-      if (all && ((r = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) ||
-                  (r = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * (size_t)std::max(nChunks, points))) || (r = grow(ctx, ctx->wPlanesStale, 4u * (size_t)nChunks))))
-         return r;
-      return NFCGPU_OK;
-   };
+   /* (a grid has at most 65535 blocks in y: beyond 2^24 tiles in one job the kernel strides) */
+   W.tilesGridY = (tilesMost + 255) / 256 > 65535u ? 65535u : (tilesMost + 255) / 256;
+}
 
-   if (under)
+/* the front-end planes: 16 bytes per sample of the submission, whole tiles (64 GiB for 4096 streams x 2^20) */
+size_t planes_bytes(const WindowedSubmission &W)
+{
+   return (size_t)W.tiles * NFC_SCAN_TILE * 16u;
+}
+
+/* room for the planes, for a list of `listed` chunks or pieces to walk for them and, `stale`, for the marks of the chunks whose start
+ * state is rewritten under a walk beside the rounds. Grows ctx->wPlanes, wPlaneChunks, wPlanesStale; queues nothing. */
+int grow_planes(nfcgpu_ctx *ctx, const WindowedSubmission &W, size_t listed, bool stale)
+{
+   int r;
+   if ((r = grow(ctx, ctx->wPlanes, planes_bytes(W))) || (r = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * listed)))
+      return r;
+   return stale ? grow(ctx, ctx->wPlanesStale, 4u * (size_t)W.nChunks) : NFCGPU_OK;
+}
+
+/* The buffers the front writes and the tail still reads. Under a pending tail the front takes the second set of them (grown
+ * here to everything the front may ask for, so that nothing is grown while it runs); a second set the device cannot give
+ * means no overlap for this context - never the fallbacks of without_the_memory.
+ *
+ * Reads the sizes of the plan; grows the current front set (`all`: the planes' buffers too, as large as any way through the front
+ * may ask for them); queues nothing. */
+int grow_front(nfcgpu_ctx *ctx, const WindowedSubmission &W, bool all)
+{
+   const uint32_t nJobs = W.nJobs, nChunks = W.nChunks, tiles = W.tiles, points = W.points;
+   int r;
+   if ((r = grow(ctx, ctx->wJobs, sizeof(NfcScanJob) * nJobs)) || (r = grow(ctx, ctx->wChunks, sizeof(NfcScanChunk) * nChunks)) ||
+       (r = grow(ctx, ctx->wPoints, sizeof(NfcScanPoint) * (size_t)points)) || (r = grow(ctx, ctx->wSeams, sizeof(NfcScanSeam) * nChunks)) ||
+       (r = grow(ctx, ctx->wChunkEdge, 4 * (size_t)nChunks)) || (r = grow(ctx, ctx->wTiles, 4 * (size_t)tiles)) ||
+       (r = grow(ctx, ctx->wTileStats, sizeof(NfcScanTile) * (size_t)tiles)) ||
+       (r = grow(ctx, ctx->wCounters, 256)) || (r = grow(ctx, ctx->wRepairs, sizeof(NfcScanChunk) * nChunks)) ||
+       (r = grow(ctx, ctx->wRepairsEnv, sizeof(NfcScanChunk) * nChunks)))
+      return r;
+   return all ? grow_planes(ctx, W, std::max(nChunks, points), true) : NFCGPU_OK;
+}
+
+/* A front under the pending tail takes the second buffer set (the sets change places: the context's members are the front's from
+ * here on). A set the device cannot give: the sets change back, the tail is completed, W.under is dropped and - out of memory -
+ * the context stops asking (noSecondSet), giving back what it got. Returns an error only for what ends the call. Queues nothing;
+ * waits for the tail's streams when it gives up. */
+int take_second_set(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   swap_front_sets(ctx);
+   ctx->growingSecond = true;
+   int rc = grow_front(ctx, W, true);
+   ctx->growingSecond = false;
+
+   if (rc)
    {
+      (void)hipGetLastError();
       swap_front_sets(ctx);
-      ctx->growingSecond = true;
-      rc = growFront(true);
-      ctx->growingSecond = false;
+      W.under = false;
+      if (rc == NFCGPU_ENOMEM)
+         ctx->noSecondSet = true;
+      const int settled = settle_tail(ctx);
 
-      if (rc)
-      {
-         (void)hipGetLastError();
-         swap_front_sets(ctx);
-         under = false;
-         if (rc == NFCGPU_ENOMEM)
-            ctx->noSecondSet = true;
-         const int settled = settle_tail(ctx);
+      /* (what was given of the second set before the device ran out goes back: it must not be what a later growth of the lane
+       * buffers finds missing) */
+      if (ctx->noSecondSet)
+         for (nfcgpu_ctx::DevBuf &b: ctx->otherSet)
+         {
+            if (b.ptr)
+               (void)hipFree(b.ptr);
+            b.ptr = nullptr;
+            b.bytes = 0;
+         }
 
-         /* (what was given of the second set before the device ran out goes back: it must not be what a later growth of the lane
-          * buffers finds missing) */
-         if (ctx->noSecondSet)
-            for (nfcgpu_ctx::DevBuf &b: ctx->otherSet)
-            {
-               if (b.ptr)
-                  (void)hipFree(b.ptr);
-               b.ptr = nullptr;
-               b.bytes = 0;
-            }
-
-         if (settled)
-            return settled;
-         if (rc != NFCGPU_ENOMEM)
-            return rc;
-         ctx->lastError.clear();
-      }
+      if (settled)
+         return settled;
+      if (rc != NFCGPU_ENOMEM)
+         return rc;
+      ctx->lastError.clear();
    }
 
-   if (!under && (rc = growFront(false)))
-      return withoutTheMemory(rc);
+   return NFCGPU_OK;
+}
 
-   uint32_t *counters = (uint32_t *)ctx->wCounters.ptr;
+/* What the kernels of the submission are given (W.A, W.dCfg, W.counters): the current front set's buffers, the plan's sizes, and
+ * the states the front starts from - the shadow states under a tail, the slots otherwise. The lanes' buffers and the planes
+ * are filled in by the stages that grow them. Queues nothing. */
+void fill_scan_args(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   NfcScanArgs &A = W.A;
+   uint32_t *counters = W.counters = (uint32_t *)ctx->wCounters.ptr;
 
-   NfcScanArgs A;
    std::memset(&A, 0, sizeof(A));
    A.jobs = (NfcScanJob *)ctx->wJobs.ptr;
-   A.nJobs = nJobs;
+   A.nJobs = W.nJobs;
    A.chunks = (const NfcScanChunk *)ctx->wChunks.ptr;
-   A.nChunks = nChunks;
-   A.stride = stride;
-   A.params = sp;
-   A.states = under ? (const NfcStreamState *)ctx->wShadow.ptr : ctx->dStates;
+   A.nChunks = W.nChunks;
+   A.stride = W.stride;
+   A.params = W.sp;
+   A.states = W.under ? (const NfcStreamState *)ctx->wShadow.ptr : ctx->dStates;
    A.points = (NfcScanPoint *)ctx->wPoints.ptr;
    A.seams = (NfcScanSeam *)ctx->wSeams.ptr;
    A.chunkEdge = (uint32_t *)ctx->wChunkEdge.ptr;
    A.tiles = (uint32_t *)ctx->wTiles.ptr;
    A.tileStats = (NfcScanTile *)ctx->wTileStats.ptr;
-   A.finalLaneSlot = finalLaneSlot;
-   A.firstWindowSlot = firstWindowSlot;
+   A.finalLaneSlot = W.finalLaneSlot;
+   A.firstWindowSlot = W.firstWindowSlot;
    A.windowCount = counters;
    A.rerunCount = counters + 1;
    A.runCount = counters + 2;
@@ -2032,516 +2099,651 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
    A.repairEnvCount = counters + 9;
    A.saveNext = counters + 8;
 
-   const NfcConfig *dCfg = ctx->dConfigs + config;
+   W.dCfg = ctx->dConfigs + W.config;
+}
 
-   auto stageBegan = entered;
-   auto mark = [&](const char *what) {
-      if (!debugStages)
-         return;
-      (void)hipStreamSynchronize(ctx->stream);
-      const auto now = std::chrono::steady_clock::now();
-      std::fprintf(stderr, "[nfcgpu] windowed stage %-10s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - stageBegan).count());
-      stageBegan = now;
-   };
+/* ---- the front: on F.fs, from A.states ---- */
 
-   /* (a grid has at most 65535 blocks in y: beyond 2^24 tiles in one job the kernel strides) */
-   const uint32_t tilesGridY = (tilesMost + 255) / 256 > 65535u ? 65535u : (tilesMost + 255) / 256;
+/* one walk of the front. `beneath`: under the pending tail, which is advanced while the front's host waits last; `redo`: walked
+ * again after the comparison (the statistics have counted its samples and second walks) */
+struct FrontPass
+{
+   hipStream_t fs;
+   bool beneath, redo;
+};
 
-   bool routed = false; /* the front has handed the whole submission to somebody else (blocks, quarters, the sequential kernels): its result is the call's */
+/* Whatever way the front is left while its stream is not the context's own: nobody reuses what it reads or writes while it runs */
+struct FrontGuard
+{
+   hipStream_t fs;
+   bool armed;
+   ~FrontGuard()
+   {
+      if (armed)
+         (void)hipStreamSynchronize(fs);
+   }
+};
 
-   /* ---- the front: on `fs`, from A.states. `beneath`: under the pending tail, which is advanced while the front's host waits last;
-    * `redo`: walked again after the comparison (the statistics have counted its samples and second walks) ---- */
-   auto front = [&](hipStream_t fs, bool beneath, bool redo) -> int {
-      /* Whatever way the front is left while its stream is not the context's own: nobody reuses what it reads or writes while it runs */
-      struct FrontGuard
-      {
-         hipStream_t fs;
-         bool armed;
-         ~FrontGuard()
-         {
-            if (armed)
-               (void)hipStreamSynchronize(fs);
-         }
-      } frontGuard {fs, beneath};
+/* the walk that writes the planes beside the rounds, on ctx->low, likewise */
+struct PlanesGuard
+{
+   nfcgpu_ctx *ctx;
+   bool running;
+   ~PlanesGuard()
+   {
+      if (running)
+         (void)hipStreamSynchronize(ctx->low); /* (whatever way the function is left: nobody reuses what the walk reads or writes while it runs) */
+   }
+};
 
-      /* a host wait of the front: under a pending tail the host goes on with that instead of sleeping */
-      auto waitFront = [&]() -> int {
-         if (!beneath)
-         {
-            HIP_TRY(ctx, hipStreamSynchronize(fs));
-            return NFCGPU_OK;
-         }
+/* a host wait of the front: under a pending tail the host goes on with that instead of sleeping */
+int wait_front(nfcgpu_ctx *ctx, const FrontPass &F)
+{
+   const hipStream_t fs = F.fs;
 
-         HIP_TRY(ctx, hipEventRecord(ctx->frontEvent, fs));
+   if (!F.beneath)
+   {
+      HIP_TRY(ctx, hipStreamSynchronize(fs));
+      return NFCGPU_OK;
+   }
 
-         for (;;)
-         {
-            int r = tail_advance(ctx, false);
-            if (r)
-               return r;
+   HIP_TRY(ctx, hipEventRecord(ctx->frontEvent, fs));
+
+   for (;;)
+   {
+      int r = tail_advance(ctx, false);
+      if (r)
+         return r;
 #ifdef NFCGPU_EMULATED_TEST_BUILD
-            HIP_TRY(ctx, hipEventSynchronize(ctx->frontEvent)); /* (synchronous streams: the tail has been given its turn, the front's work is done) */
-            break;
+      HIP_TRY(ctx, hipEventSynchronize(ctx->frontEvent)); /* (synchronous streams: the tail has been given its turn, the front's work is done) */
+      break;
 #else
-            const hipError_t q = hipEventQuery(ctx->frontEvent);
-            if (q == hipSuccess)
-               break;
-            if (q != hipErrorNotReady)
-               return fail(ctx, NFCGPU_EHIP, "hipEventQuery(ctx->frontEvent)", q);
-            if (!ctx->tail)
-            {
-               HIP_TRY(ctx, hipEventSynchronize(ctx->frontEvent));
-               break;
-            }
-            std::this_thread::sleep_for(std::chrono::microseconds(20)); /* (two events to look at, milliseconds apart: no need to spin) */
+      const hipError_t q = hipEventQuery(ctx->frontEvent);
+      if (q == hipSuccess)
+         break;
+      if (q != hipErrorNotReady)
+         return fail(ctx, NFCGPU_EHIP, "hipEventQuery(ctx->frontEvent)", q);
+      if (!ctx->tail)
+      {
+         HIP_TRY(ctx, hipEventSynchronize(ctx->frontEvent));
+         break;
+      }
+      std::this_thread::sleep_for(std::chrono::microseconds(20)); /* (two events to look at, milliseconds apart: no need to spin) */
 #endif
-         }
+   }
 
-         return NFCGPU_OK;
-      };
+   return NFCGPU_OK;
+}
 
-      auto leave = [&](int code) -> int {
-         routed = true;
-         return code;
-      };
+/* (the front leaves the submission to somebody else: whatever is pending is completed first, and the front's stream is idle - callers are behind a wait) */
+int hand_over(nfcgpu_ctx *ctx, const FrontPass &F)
+{
+   if (F.beneath)
+   {
+      (void)hipStreamSynchronize(F.fs);
+      return settle_tail(ctx);
+   }
+   return NFCGPU_OK;
+}
 
-      /* (the front leaves the submission to somebody else: whatever is pending is completed first, and the front's stream is idle - callers are behind a wait) */
-      auto handOver = [&]() -> int {
-         if (beneath)
-         {
-            (void)hipStreamSynchronize(fs);
-            return settle_tail(ctx);
-         }
-         return NFCGPU_OK;
-      };
+/* the front cannot get a buffer: handed over, then the fallbacks of without_the_memory. Writes W.routed. */
+int front_no_memory(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F, int code)
+{
+   const int handed = hand_over(ctx, F);
+   W.routed = true;
+   return handed ? handed : without_the_memory(ctx, W, code);
+}
 
-      auto noMemory = [&](int code) -> int {
-         const int handed = handOver();
-         return leave(handed ? handed : withoutTheMemory(code));
-      };
+/* a few long busy streams (front_seam_round): handed over, then block by block. Writes W.routed. */
+int front_in_blocks(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F)
+{
+   const int handed = hand_over(ctx, F);
+   W.routed = true;
+   return handed ? handed : run_in_blocks(ctx, W.config, W.items, W.stride);
+}
 
-      auto inBlocks = [&]() -> int {
-         const int handed = handOver();
-         return leave(handed ? handed : run_in_blocks(ctx, config, items, stride));
-      };
+/* Upload and first scan. Reads W.jobs and W.chunks (host) and the samples; writes the job and chunk tables, the counters and every
+ * record of the scan in the current front set, and resets A.planes / A.planesStale (a second front starts as the first did). All
+ * on F.fs, which under a tail first waits for the pending submission's first pass. Counts scan_samples unless `redo`. */
+int front_scan(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F)
+{
+   const hipStream_t fs = F.fs;
+   const bool beneath = F.beneath, redo = F.redo;
+   NfcScanArgs &A = W.A;
+   const std::vector<NfcScanJob> &jobs = W.jobs;
+   const std::vector<NfcScanChunk> &chunks = W.chunks;
+   const uint32_t nJobs = W.nJobs, nChunks = W.nChunks, tilesGridY = W.tilesGridY, tilesMost = W.tilesMost;
+   const uint64_t totalSamples = W.totalSamples;
+   const NfcConfig *dCfg = W.dCfg;
+   uint32_t *counters = W.counters;
 
-      A.planes = nullptr;
-      A.planesStale = nullptr;
+   A.planes = nullptr;
+   A.planesStale = nullptr;
 
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->wJobs.ptr, jobs.data(), sizeof(NfcScanJob) * nJobs, hipMemcpyHostToDevice, fs));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->wChunks.ptr, chunks.data(), sizeof(NfcScanChunk) * nChunks, hipMemcpyHostToDevice, fs));
-      HIP_TRY(ctx, hipMemsetAsync(counters, 0, 256, fs));
+   HIP_TRY(ctx, hipMemcpyAsync(ctx->wJobs.ptr, jobs.data(), sizeof(NfcScanJob) * nJobs, hipMemcpyHostToDevice, fs));
+   HIP_TRY(ctx, hipMemcpyAsync(ctx->wChunks.ptr, chunks.data(), sizeof(NfcScanChunk) * nChunks, hipMemcpyHostToDevice, fs));
+   HIP_TRY(ctx, hipMemsetAsync(counters, 0, 256, fs));
 
-      /* under the tail: not before the pending submission's first pass is over (the event its chain state waits for) - that pass has
-       * the device to itself -, which is also behind the shadow states this front starts from */
-      if (beneath && ctx->tail)
-         HIP_TRY(ctx, hipStreamWaitEvent(fs, ctx->tail->ready, 0));
+   /* under the tail: not before the pending submission's first pass is over (the event its chain state waits for) - that pass has
+    * the device to itself -, which is also behind the shadow states this front starts from */
+   if (beneath && ctx->tail)
+      HIP_TRY(ctx, hipStreamWaitEvent(fs, ctx->tail->ready, 0));
 
-      mark("tables");
+   mark_stage(ctx, W, "tables");
 
-      /* scan */
-      ProfiledLaunch pl {nullptr, nullptr};
-      record_span(ctx, ctx->timedScan, pl, true, fs);
-      hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_scan_kernel), dim3((nChunks + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, A);
-      HIP_TRY(ctx, hipGetLastError());
-      record_span(ctx, ctx->timedScan, pl, false, fs);
-      if (!redo)
-         ctx->stats.scan_samples += totalSamples;
+   /* scan */
+   ProfiledLaunch pl {nullptr, nullptr};
+   record_span(ctx, ctx->timedScan, pl, true, fs);
+   hipLaunchKernelGGL(NFC_BY_LAYOUT(A.stride, nfc_scan_kernel), dim3((nChunks + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, A);
+   HIP_TRY(ctx, hipGetLastError());
+   record_span(ctx, ctx->timedScan, pl, false, fs);
+   if (!redo)
+      ctx->stats.scan_samples += totalSamples;
 
-      mark("scan");
+   mark_stage(ctx, W, "scan");
 
-      /* a first run of the tile tests: how busy is each stream? Only a small submission is routed by that (below: `small`); a large
-       * one gets its tile flags once, when the envelopes they are formed from are the true ones (3.8 ms for the 67 M tiles of config 5) */
-      if (nJobs < NFC_LANES && !ctx->inBlocks)
-      {
-         hipLaunchKernelGGL(nfc_tiles_kernel, dim3(nJobs, tilesGridY), dim3(256), 0, fs, dCfg, A, tilesMost);
-         HIP_TRY(ctx, hipGetLastError());
-      }
-
-      /* The front-end planes (below) are a walk of every chunk from its verified start state: 69 GB of stores for config 5, 32 ms
-       * of a device that the rounds of second walks after the first leave nearly idle (a few thousand chunks each, as long as
-       * their longest chain). Round 5: for a large submission that walk is started on a stream of its own (lowest priority) as soon as the first round's
-       * second walks are queued - by then nine chunks in ten start from their true state -, the seam check and the envelope
-       * walks note every start state they rewrite from then on (NfcScanArgs::planesStale), and those chunks' planes are written
-       * again when the rounds are over. */
-      const bool planesBeside = ctx->planesBeside && ctx->low != nullptr && totalSamples > (4u << 20);
-      bool planesStarted = false;
-
-      struct PlanesGuard
-      {
-         nfcgpu_ctx *ctx;
-         bool running;
-         ~PlanesGuard()
-         {
-            if (running)
-               (void)hipStreamSynchronize(ctx->low); /* (whatever way the function is left: nobody reuses what the walk reads or writes while it runs) */
-         }
-      } planesGuard {ctx, false};
-
-      if (planesBeside)
-      {
-         if ((rc = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) || (rc = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * nChunks)) ||
-             (rc = grow(ctx, ctx->wPlanesStale, 4u * (size_t)nChunks)))
-            return noMemory(rc);
-
-         HIP_TRY(ctx, hipMemsetAsync(ctx->wPlanesStale.ptr, 0, 4u * (size_t)nChunks, fs));
-      }
-
-      /* seams: chunks that did not start from the true state are walked again, a round at a time */
-
-      for (uint32_t round = 0;; round++)
-      {
-         if (debugStages && std::atoi(std::getenv("NFCGPU_WINDOW_DEBUG")) >= 4)
-         {
-            /* which fields keep seams from verifying (host-side look at the records the seam check is about to judge) */
-            std::vector<NfcScanSeam> sm(nChunks);
-            if ((rc = waitFront()))
-               return rc;
-            HIP_TRY(ctx, hipMemcpy(sm.data(), ctx->wSeams.ptr, sizeof(NfcScanSeam) * nChunks, hipMemcpyDeviceToHost));
-            uint32_t n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (uint32_t j = 0; j < nJobs; j++)
-               for (uint32_t k = 1; k < jobs[j].chunks; k++)
-               {
-                  const NfcScanPoint &a = sm[jobs[j].firstChunk + k].start, &b = sm[jobs[j].firstChunk + k - 1].end;
-                  const bool env = std::memcmp(&a.env, &b.env, 4) != 0 || a.pulseFilter != b.pulseFilter;
-                  const bool n1 = std::memcmp(&a.n1, &b.n1, 4) != 0, mdev = std::memcmp(&a.mdev, &b.mdev, 4) != 0, avg = std::memcmp(&a.avg, &b.avg, 4) != 0;
-                  const bool peak = std::memcmp(&a.edgePeak, &b.edgePeak, 4) != 0, zone = ((a.zone ^ b.zone) & 0xFFu) != 0;
-                  const bool time = (a.zone & 0x100u) && (b.zone & 0x100u) && a.edgeTime != b.edgeTime;
-                  n[0] += env; n[1] += n1; n[2] += mdev; n[3] += avg; n[4] += peak; n[5] += zone; n[6] += time;
-                  n[7] += (n1 || mdev || avg || peak || zone) ? 1u : 0u;
-               }
-            std::fprintf(stderr, "[nfcgpu]    before round %u, seams that differ in: envelope / counter %u, n1 %u, deviation %u, average %u, edge peak %u, zone %u, known edge times %u; in anything but the envelope %u\n",
-                         round, n[0], n[1], n[2], n[3], n[4], n[5], n[6], n[7]);
-         }
-
-         HIP_TRY(ctx, hipMemsetAsync(counters + 7, 0, 4, fs));
-         HIP_TRY(ctx, hipMemsetAsync(counters + 9, 0, 4, fs));
-         hipLaunchKernelGGL(nfc_seams_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, fs, A, round == 0 ? 1u : 0u);
-         HIP_TRY(ctx, hipGetLastError());
-
-         /* chunks to walk again: every recurrence of them (A.repairs), the envelope tracker alone (A.repairsEnv: listed apart by
-          * the seam check when the envelope kernel is on) */
-         uint32_t *word = ctx->frontHost; /* (pinned: the copy does not hold the host, which has a tail to advance) */
-         HIP_TRY(ctx, hipMemcpyAsync(word, counters + 7, 12, hipMemcpyDeviceToHost, fs));
-
-         /* (a small submission: how busy are its streams? the tile tests have counted) */
-         const bool small = round == 0 && nJobs < NFC_LANES && !ctx->inBlocks;
-         if (small)
-            HIP_TRY(ctx, hipMemcpyAsync(jobs.data(), ctx->wJobs.ptr, sizeof(NfcScanJob) * nJobs, hipMemcpyDeviceToHost, fs));
-
-         if ((rc = waitFront()))
-            return rc;
-         const uint32_t whole = word[0], alone = word[2];
-         const uint32_t repairs = whole + alone;
-
-         /* A few long busy streams: the passes the chain needs grow with the length of the submission (a frame that changes
-          * the protocol timing is learnt one generation per pass), so it is decoded in blocks, each settled before the next.
-          * Nothing has been touched yet (the scan only reads). */
-         if (small)
-         {
-            uint32_t longest = 0;
-            bool busy = false;
-
-            for (uint32_t j = 0; j < nJobs; j++)
-            {
-               const uint64_t nTiles = ((uint64_t)jobs[j].count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE;
-               busy = busy || (uint64_t)jobs[j].busyTiles * 100u > nTiles * ctx->busyPercent;
-               longest = jobs[j].count > longest ? jobs[j].count : longest;
-            }
-
-            if (busy && longest > ctx->blockSamples)
-               return inBlocks();
-         }
-
-         if (debugStages)
-            std::fprintf(stderr, "[nfcgpu]    seams round %u: %u chunks to walk again\n", round, repairs);
-
-         if (!repairs)
-            break;
-
-         /* The chunks whose envelope tracker alone started wrong - from the second round on that is all of them: chains of chunks
-          * that inherit a wrong envelope from each other, a chunk per round - go to a kernel that does nothing else, a wavefront
-          * per chunk (nfc_envelope.hpp): a round then costs the tracker's own latency over one chunk instead of the scan kernel's
-          * row machinery over it (9 ms of 32768 samples, however short the list). A list too long for a wave a chunk to pay (the
-          * first round of a large submission: a quarter of its chunks, the scan kernel's 64 chunks per wave are the better use
-          * of the machine) stays with the scan kernel's envelope-only branch (NFCGPU_ENVELOPE_KERNEL: the longest list the
-          * envelope kernel is given). */
-         if (debugStages && alone && alone <= ctx->envelopeMax)
-            std::fprintf(stderr, "[nfcgpu]    ... %u of them the envelope tracker's alone, by the envelope kernel\n", alone);
-
-         ProfiledLaunch pr {nullptr, nullptr};
-         record_span(ctx, ctx->timedScan, pr, true, fs);
-
-         const bool byWaves = alone && alone <= ctx->envelopeMax;
-
-         if (whole || (alone && !byWaves))
-         {
-            /* the scan kernel: the chunks walked whole, and a list of envelope-only ones too long for a wave each, in one launch */
-            NfcScanArgs R = A;
-            R.chunks = A.repairs;
-            R.nChunks = whole;
-            R.chunksMore = byWaves ? nullptr : A.repairsEnv;
-            R.nChunksMore = byWaves ? 0u : alone;
-
-            const uint32_t listedNow = R.nChunks + R.nChunksMore;
-
-            hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_scan_kernel), dim3((listedNow + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, R);
-            HIP_TRY(ctx, hipGetLastError());
-         }
-
-         if (byWaves)
-         {
-            NfcScanArgs R = A;
-            R.chunks = A.repairsEnv;
-            R.nChunks = alone;
-            R.followChains = alone <= ctx->envelopeFollowMax ? 1u : 0u;
-
-            hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_envelope_kernel), dim3(alone), dim3(NFC_LANES), 0, fs, dCfg, R);
-            HIP_TRY(ctx, hipGetLastError());
-         }
-
-         record_span(ctx, ctx->timedScan, pr, false, fs);
-         if (!redo)
-            ctx->stats.scan_repairs += repairs;
-
-         if (planesBeside && round == 0)
-         {
-            /* the planes of every chunk, beside the rounds to come */
-            HIP_TRY(ctx, hipEventRecord(ctx->planesFork, fs));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->low, ctx->planesFork, 0));
-            planesGuard.running = true;
-
-            NfcScanArgs P = A;
-            P.planes = (float *)ctx->wPlanes.ptr;
-            P.chunks = (const NfcScanChunk *)ctx->wChunks.ptr; /* (the submission's chunk table as it is: the walk takes no notice of the repair marks) */
-            P.nChunks = nChunks;
-            /* a lane per piece, and the pieces of a chunk have to tile it: the largest multiple of the distance of the stored
-             * points (every lane starts from one) that is no longer than NFCGPU_PLANES_BESIDE_PIECE and divides the chunk. (Until
-             * round 6 the quotient was truncated: with a chunk that is no multiple of the piece - the default sizing gives any
-             * multiple of 512 for totals between 2^28 and 2^30 samples - the tail of every chunk that was not walked again got no
-             * planes at all.) A chunk is a multiple of the points' distance, so that distance always does. */
-            P.planesPiece = ctx->planesBesidePiece / NFC_SCAN_POINT * NFC_SCAN_POINT;
-            if (P.planesPiece > sp.chunkSamples)
-               P.planesPiece = sp.chunkSamples / NFC_SCAN_POINT * NFC_SCAN_POINT;
-            while (P.planesPiece > NFC_SCAN_POINT && sp.chunkSamples % P.planesPiece != 0u)
-               P.planesPiece -= NFC_SCAN_POINT;
-            if (P.planesPiece && sp.chunkSamples % P.planesPiece != 0u)
-               P.planesPiece = 0u; /* (a chunk that is no multiple of the points' distance: a lane per chunk, from its start) */
-            P.planesPerChunk = P.planesPiece ? sp.chunkSamples / P.planesPiece : 0u;
-
-            const uint64_t lanesOfIt = (uint64_t)nChunks * (P.planesPerChunk ? P.planesPerChunk : 1u);
-
-            ProfiledLaunch pp {nullptr, nullptr};
-            record_span(ctx, ctx->timedPlanes, pp, true, ctx->low);
-            hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)((lanesOfIt + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->low, dCfg, P);
-            HIP_TRY(ctx, hipGetLastError());
-            record_span(ctx, ctx->timedPlanes, pp, false, ctx->low);
-            HIP_TRY(ctx, hipEventRecord(ctx->planesJoin, ctx->low));
-
-            planesStarted = true;
-            A.planesStale = (uint32_t *)ctx->wPlanesStale.ptr; /* from the next round on */
-         }
-      }
+   /* a first run of the tile tests: how busy is each stream? Only a small submission is routed by that (below: `small`); a large
+    * one gets its tile flags once, when the envelopes they are formed from are the true ones (3.8 ms for the 67 M tiles of config 5) */
+   if (nJobs < NFC_LANES && !ctx->inBlocks)
+   {
       hipLaunchKernelGGL(nfc_tiles_kernel, dim3(nJobs, tilesGridY), dim3(256), 0, fs, dCfg, A, tilesMost);
       HIP_TRY(ctx, hipGetLastError());
+   }
 
-      mark("seams");
+   return NFCGPU_OK;
+}
 
-      /* The wave decoder takes the front end's results per sample instead of walking it again: a second walk of every
-       * chunk from its verified start state (the repair form of the scan: no warm-up) writes them. */
-      if (planesStarted)
+/* Room for a planes walk beside the rounds (grow_planes) and its marks cleared, on F.fs. Without the memory the submission is
+ * routed (front_no_memory). */
+int front_beside_room(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F)
+{
+   const hipStream_t fs = F.fs;
+   const uint32_t nChunks = W.nChunks;
+   int rc;
+
+   if ((rc = grow_planes(ctx, W, nChunks, true)))
+      return front_no_memory(ctx, W, F, rc);
+
+   HIP_TRY(ctx, hipMemsetAsync(ctx->wPlanesStale.ptr, 0, 4u * (size_t)nChunks, fs));
+   return NFCGPU_OK;
+}
+
+/* NFCGPU_WINDOW_DEBUG=4: which fields keep seams from verifying (host-side look at the records the seam check is about to judge).
+ * Waits for the front and copies the seam records back; changes nothing. */
+int dump_seams(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F, uint32_t round)
+{
+   const std::vector<NfcScanJob> &jobs = W.jobs;
+   const uint32_t nJobs = W.nJobs, nChunks = W.nChunks;
+   int rc;
+
+   std::vector<NfcScanSeam> sm(nChunks);
+   if ((rc = wait_front(ctx, F)))
+      return rc;
+   HIP_TRY(ctx, hipMemcpy(sm.data(), ctx->wSeams.ptr, sizeof(NfcScanSeam) * nChunks, hipMemcpyDeviceToHost));
+   uint32_t n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+   for (uint32_t j = 0; j < nJobs; j++)
+      for (uint32_t k = 1; k < jobs[j].chunks; k++)
       {
-         /* the walk over all chunks has run beside the rounds: the chunks whose start state changed under it, again */
-         HIP_TRY(ctx, hipStreamWaitEvent(fs, ctx->planesJoin, 0));
-         planesGuard.running = false; /* (the main stream now waits for it) */
-
-         HIP_TRY(ctx, hipMemsetAsync(counters + 11, 0, 4, fs));
-         hipLaunchKernelGGL(nfc_planes_stale_kernel, dim3((nChunks + 255) / 256), dim3(256), 0, fs, A, (const NfcScanChunk *)ctx->wChunks.ptr, nChunks,
-                            (NfcScanChunk *)ctx->wPlaneChunks.ptr, counters + 11);
-         HIP_TRY(ctx, hipGetLastError());
-
-         uint32_t &again = ctx->frontHost[4];
-         HIP_TRY(ctx, hipMemcpyAsync(ctx->frontHost + 4, counters + 11, 4, hipMemcpyDeviceToHost, fs));
-         if ((rc = waitFront()))
-            return rc;
-
-         A.planes = (float *)ctx->wPlanes.ptr;
-         A.planesStale = nullptr;
-
-         if (debugStages)
-            std::fprintf(stderr, "[nfcgpu]    planes written beside the rounds; %u chunks of %u again\n", again, nChunks);
-
-         if (again)
-         {
-            NfcScanArgs P = A;
-            /* (a stored point per lane - 512 samples, from the points the rounds have left true -: a few thousand chunks a lane each
-             * would take as long as one chunk's walk, 12 ms, with the device all but idle) */
-            P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
-            P.nChunks = again;
-            P.planesPiece = NFC_SCAN_POINT;
-            P.planesPerChunk = sp.chunkSamples / NFC_SCAN_POINT;
-
-            ProfiledLaunch pp {nullptr, nullptr};
-            record_span(ctx, ctx->timedPlanes, pp, true, fs);
-            hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)(((uint64_t)again * P.planesPerChunk + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, fs, dCfg, P);
-            HIP_TRY(ctx, hipGetLastError());
-            record_span(ctx, ctx->timedPlanes, pp, false, fs);
-         }
-
-         mark("planes");
+         const NfcScanPoint &a = sm[jobs[j].firstChunk + k].start, &b = sm[jobs[j].firstChunk + k - 1].end;
+         const bool env = std::memcmp(&a.env, &b.env, 4) != 0 || a.pulseFilter != b.pulseFilter;
+         const bool n1 = std::memcmp(&a.n1, &b.n1, 4) != 0, mdev = std::memcmp(&a.mdev, &b.mdev, 4) != 0, avg = std::memcmp(&a.avg, &b.avg, 4) != 0;
+         const bool peak = std::memcmp(&a.edgePeak, &b.edgePeak, 4) != 0, zone = ((a.zone ^ b.zone) & 0xFFu) != 0;
+         const bool time = (a.zone & 0x100u) && (b.zone & 0x100u) && a.edgeTime != b.edgeTime;
+         n[0] += env; n[1] += n1; n[2] += mdev; n[3] += avg; n[4] += peak; n[5] += zone; n[6] += time;
+         n[7] += (n1 || mdev || avg || peak || zone) ? 1u : 0u;
       }
-      else
-      {
-         /* A small submission - one a caller waits for - is walked a lane per stored point instead of a lane per chunk: 512 samples
-          * instead of 4096 on the way of everything that follows (NFCGPU_PLANES_PIECE; a short capture: 1.1 -> 0.2 ms) */
-         const uint32_t piece = totalSamples <= (4u << 20) ? ctx->planesPiece / NFC_SCAN_POINT * NFC_SCAN_POINT : 0u;
+   std::fprintf(stderr, "[nfcgpu]    before round %u, seams that differ in: envelope / counter %u, n1 %u, deviation %u, average %u, edge peak %u, zone %u, known edge times %u; in anything but the envelope %u\n",
+                round, n[0], n[1], n[2], n[3], n[4], n[5], n[6], n[7]);
+   return NFCGPU_OK;
+}
 
-         std::vector<NfcScanChunk> all;
+/* One seam round on F.fs: the seam check, its counts to the host (a host wait), and the second walks of the chunks it listed -
+ * the scan kernel, the envelope kernel or both. *found: the chunks walked again; none ends the rounds. Round 0 of a small
+ * submission also reads the job table back into W.jobs (the tile tests have counted its busy tiles) and may route the submission
+ * to blocks (W.routed). Reads and rewrites the seam and point records of the current front set; counts scan_repairs unless `redo`. */
+int front_seam_round(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F, uint32_t round, uint32_t *found)
+{
+   const hipStream_t fs = F.fs;
+   const bool redo = F.redo;
+   const NfcScanArgs &A = W.A;
+   std::vector<NfcScanJob> &jobs = W.jobs;
+   const uint32_t nJobs = W.nJobs;
+   const bool debugStages = W.debugStages;
+   const NfcConfig *dCfg = W.dCfg;
+   uint32_t *counters = W.counters;
+   int rc;
 
-         if (piece)
-         {
-            for (uint32_t j = 0; j < nJobs; j++)
-               for (uint32_t i = 0; i * piece < jobs[j].count; i++)
-                  all.push_back(NfcScanChunk {j, i | NFC_CHUNK_REPAIR});
-         }
-         else
-         {
-            all = chunks;
-            for (NfcScanChunk &c: all)
-               c.index |= NFC_CHUNK_REPAIR;
-         }
+   HIP_TRY(ctx, hipMemsetAsync(counters + 7, 0, 4, fs));
+   HIP_TRY(ctx, hipMemsetAsync(counters + 9, 0, 4, fs));
+   hipLaunchKernelGGL(nfc_seams_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, fs, A, round == 0 ? 1u : 0u);
+   HIP_TRY(ctx, hipGetLastError());
 
-         const uint32_t nPlaneLanes = (uint32_t)all.size();
+   /* chunks to walk again: every recurrence of them (A.repairs), the envelope tracker alone (A.repairsEnv: listed apart by
+    * the seam check when the envelope kernel is on) */
+   uint32_t *word = ctx->frontHost; /* (pinned: the copy does not hold the host, which has a tail to advance) */
+   HIP_TRY(ctx, hipMemcpyAsync(word, counters + 7, 12, hipMemcpyDeviceToHost, fs));
 
-         if ((rc = grow(ctx, ctx->wPlanes, (size_t)tiles * NFC_SCAN_TILE * 16u)) || (rc = grow(ctx, ctx->wPlaneChunks, sizeof(NfcScanChunk) * all.size())))
-         {
-            /* (the planes are 16 bytes per sample of the submission: 64 GiB for 4096 streams x 2^20) */
-            return noMemory(rc);
-         }
+   /* (a small submission: how busy are its streams? the tile tests have counted) */
+   const bool small = round == 0 && nJobs < NFC_LANES && !ctx->inBlocks;
+   if (small)
+      HIP_TRY(ctx, hipMemcpyAsync(jobs.data(), ctx->wJobs.ptr, sizeof(NfcScanJob) * nJobs, hipMemcpyDeviceToHost, fs));
 
-         HIP_TRY(ctx, hipMemcpyAsync(ctx->wPlaneChunks.ptr, all.data(), sizeof(NfcScanChunk) * all.size(), hipMemcpyHostToDevice, fs));
+   if ((rc = wait_front(ctx, F)))
+      return rc;
+   const uint32_t whole = word[0], alone = word[2];
+   const uint32_t repairs = *found = whole + alone;
 
-         A.planes = (float *)ctx->wPlanes.ptr;
-
-         NfcScanArgs P = A;
-         P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
-         P.nChunks = nPlaneLanes;
-         P.planesPiece = piece;
-
-         ProfiledLaunch pp {nullptr, nullptr};
-         record_span(ctx, ctx->timedPlanes, pp, true, fs);
-         hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((nPlaneLanes + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, P);
-         HIP_TRY(ctx, hipGetLastError());
-         record_span(ctx, ctx->timedPlanes, pp, false, fs);
-         if ((rc = waitFront()))
-            return rc; /* (the chunk list is a local) */
-
-         mark("planes");
-      }
-
-      frontGuard.armed = false;
-      return NFCGPU_OK;
-   };
-
-   if (under)
+   /* A few long busy streams: the passes the chain needs grow with the length of the submission (a frame that changes
+    * the protocol timing is learnt one generation per pass), so it is decoded in blocks, each settled before the next.
+    * Nothing has been touched yet (the scan only reads). */
+   if (small)
    {
-      rc = front(ctx->front, true, false);
-      if (rc || routed)
-         return rc;
+      uint32_t longest = 0;
+      bool busy = false;
 
-      ctx->stats.pipelined_submissions++;
-
-      /* the tail, finish and any sequential fallback of its invalid jobs included; then the main stream takes the front's work in */
-      if ((rc = settle_tail(ctx)))
+      for (uint32_t j = 0; j < nJobs; j++)
       {
-         (void)hipStreamSynchronize(ctx->front);
-         return rc;
+         const uint64_t nTiles = ((uint64_t)jobs[j].count + NFC_SCAN_TILE - 1) / NFC_SCAN_TILE;
+         busy = busy || (uint64_t)jobs[j].busyTiles * 100u > nTiles * ctx->busyPercent;
+         longest = jobs[j].count > longest ? jobs[j].count : longest;
       }
 
-      HIP_TRY(ctx, hipEventRecord(ctx->frontEvent, ctx->front));
-      HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->frontEvent, 0));
+      if (busy && longest > ctx->blockSamples)
+         return front_in_blocks(ctx, W, F);
+   }
 
-      /* exact or not taken: what the finish really left in the slots against the shadow states the front started from */
-      NfcShadowArgs S;
-      std::memset(&S, 0, sizeof(S));
-      S.jobs = A.jobs;
-      S.nJobs = nJobs;
-      S.real = ctx->dStates;
-      S.shadow = (NfcStreamState *)ctx->wShadow.ptr;
-      S.ctl = (uint32_t *)ctx->wShadowCtl.ptr;
+   if (debugStages)
+      std::fprintf(stderr, "[nfcgpu]    seams round %u: %u chunks to walk again\n", round, repairs);
 
-      S.points = A.points;
-      S.renameSeams = A.seams;
-      S.renameEdge = A.chunkEdge;
+   if (!repairs)
+      return NFCGPU_OK;
 
-      HIP_TRY(ctx, hipMemsetAsync(S.ctl, 0, 64, ctx->stream));
-      hipLaunchKernelGGL(nfc_shadow_compare_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, S);
+   /* The chunks whose envelope tracker alone started wrong - from the second round on that is all of them: chains of chunks
+    * that inherit a wrong envelope from each other, a chunk per round - go to a kernel that does nothing else, a wavefront
+    * per chunk (nfc_envelope.hpp): a round then costs the tracker's own latency over one chunk instead of the scan kernel's
+    * row machinery over it (9 ms of 32768 samples, however short the list). A list too long for a wave a chunk to pay (the
+    * first round of a large submission: a quarter of its chunks, the scan kernel's 64 chunks per wave are the better use
+    * of the machine) stays with the scan kernel's envelope-only branch (NFCGPU_ENVELOPE_KERNEL: the longest list the
+    * envelope kernel is given). */
+   if (debugStages && alone && alone <= ctx->envelopeMax)
+      std::fprintf(stderr, "[nfcgpu]    ... %u of them the envelope tracker's alone, by the envelope kernel\n", alone);
+
+   ProfiledLaunch pr {nullptr, nullptr};
+   record_span(ctx, ctx->timedScan, pr, true, fs);
+
+   const bool byWaves = alone && alone <= ctx->envelopeMax;
+
+   if (whole || (alone && !byWaves))
+   {
+      /* the scan kernel: the chunks walked whole, and a list of envelope-only ones too long for a wave each, in one launch */
+      NfcScanArgs R = A;
+      R.chunks = A.repairs;
+      R.nChunks = whole;
+      R.chunksMore = byWaves ? nullptr : A.repairsEnv;
+      R.nChunksMore = byWaves ? 0u : alone;
+
+      const uint32_t listedNow = R.nChunks + R.nChunksMore;
+
+      hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_scan_kernel), dim3((listedNow + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, R);
       HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->tailHost + 16, S.ctl, 64, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+   }
 
-      const uint32_t differ = ctx->tailHost[16], zeroed = ctx->tailHost[26];
-      A.states = ctx->dStates;
+   if (byWaves)
+   {
+      NfcScanArgs R = A;
+      R.chunks = A.repairsEnv;
+      R.nChunks = alone;
+      R.followChains = alone <= ctx->envelopeFollowMax ? 1u : 0u;
 
-      if (ctx->pipelineReport && !differ)
-         std::fprintf(stderr, "[nfcgpu] pipelined front: %u streams ended on a zeroed edge time (put right in the records), none differs otherwise\n", zeroed);
+      hipLaunchKernelGGL(NFC_BY_LAYOUT(R.stride, nfc_envelope_kernel), dim3(alone), dim3(NFC_LANES), 0, fs, dCfg, R);
+      HIP_TRY(ctx, hipGetLastError());
+   }
 
-      if (!differ)
-         ctx->stats.pipeline_zeroed_edges += zeroed;
+   record_span(ctx, ctx->timedScan, pr, false, fs);
+   if (!redo)
+      ctx->stats.scan_repairs += repairs;
 
-      if (zeroed && !differ)
-      {
-         /* (a carrier frame after the tracker last moved: NfcShadowArgs) */
-         hipLaunchKernelGGL(nfc_shadow_rename_kernel, dim3(nJobs), dim3(64), 0, ctx->stream, S);
-         HIP_TRY(ctx, hipGetLastError());
-      }
+   return NFCGPU_OK;
+}
 
-      if (differ)
-      {
-         /* streams that did not end where their front-end records said (a stream the sequential kernels decoded, say): the front
-          * again, unpipelined, from the true state */
-         const uint32_t *f = ctx->tailHost + 16;
-         ctx->stats.pipeline_refronts += differ;
+/* The planes of every chunk, beside the rounds to come: on ctx->low, behind what F.fs has queued so far (planesFork); planesJoin is
+ * recorded behind the walk and `planesGuard` armed. From here on the rounds note the start states they rewrite (A.planesStale).
+ * Reads the points the first round has left; writes ctx->wPlanes. */
+int front_planes_beside(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F, PlanesGuard &planesGuard)
+{
+   const hipStream_t fs = F.fs;
+   NfcScanArgs &A = W.A;
+   const NfcScanParams &sp = W.sp;
+   const uint32_t nChunks = W.nChunks;
+   const NfcConfig *dCfg = W.dCfg;
 
-         if (ctx->pipelineReport)
-            std::fprintf(stderr, "[nfcgpu] pipelined front redone: %u streams differ from their shadow state otherwise than by a zeroed edge time (clock %u, pulse counter %u, envelope %u, n1 %u, deviation %u, average %u, "
-                                 "edge peak %u, edge time %u, carrier zone %u)\n", f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9]);
+   HIP_TRY(ctx, hipEventRecord(ctx->planesFork, fs));
+   HIP_TRY(ctx, hipStreamWaitEvent(ctx->low, ctx->planesFork, 0));
+   planesGuard.running = true;
 
-         rc = front(ctx->stream, false, true);
-         if (rc || routed)
-            return rc;
-      }
+   NfcScanArgs P = A;
+   P.planes = (float *)ctx->wPlanes.ptr;
+   P.chunks = (const NfcScanChunk *)ctx->wChunks.ptr; /* (the submission's chunk table as it is: the walk takes no notice of the repair marks) */
+   P.nChunks = nChunks;
+   /* a lane per piece, and the pieces of a chunk have to tile it: the largest multiple of the distance of the stored
+    * points (every lane starts from one) that is no longer than NFCGPU_PLANES_BESIDE_PIECE and divides the chunk. (Until
+    * round 6 the quotient was truncated: with a chunk that is no multiple of the piece - the default sizing gives any
+    * multiple of 512 for totals between 2^28 and 2^30 samples - the tail of every chunk that was not walked again got no
+    * planes at all.) A chunk is a multiple of the points' distance, so that distance always does. */
+   P.planesPiece = ctx->planesBesidePiece / NFC_SCAN_POINT * NFC_SCAN_POINT;
+   if (P.planesPiece > sp.chunkSamples)
+      P.planesPiece = sp.chunkSamples / NFC_SCAN_POINT * NFC_SCAN_POINT;
+   while (P.planesPiece > NFC_SCAN_POINT && sp.chunkSamples % P.planesPiece != 0u)
+      P.planesPiece -= NFC_SCAN_POINT;
+   if (P.planesPiece && sp.chunkSamples % P.planesPiece != 0u)
+      P.planesPiece = 0u; /* (a chunk that is no multiple of the points' distance: a lane per chunk, from its start) */
+   P.planesPerChunk = P.planesPiece ? sp.chunkSamples / P.planesPiece : 0u;
+
+   const uint64_t lanesOfIt = (uint64_t)nChunks * (P.planesPerChunk ? P.planesPerChunk : 1u);
+
+   ProfiledLaunch pp {nullptr, nullptr};
+   record_span(ctx, ctx->timedPlanes, pp, true, ctx->low);
+   hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)((lanesOfIt + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, ctx->low, dCfg, P);
+   HIP_TRY(ctx, hipGetLastError());
+   record_span(ctx, ctx->timedPlanes, pp, false, ctx->low);
+   HIP_TRY(ctx, hipEventRecord(ctx->planesJoin, ctx->low));
+
+   A.planesStale = (uint32_t *)ctx->wPlanesStale.ptr; /* from the next round on */
+   return NFCGPU_OK;
+}
+
+/* the tile flags, from the envelopes the rounds have left true: on F.fs, into A.tiles and the jobs' counts */
+int front_tile_flags(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F)
+{
+   const hipStream_t fs = F.fs;
+   const NfcScanArgs &A = W.A;
+
+   hipLaunchKernelGGL(nfc_tiles_kernel, dim3(W.nJobs, W.tilesGridY), dim3(256), 0, fs, W.dCfg, A, W.tilesMost);
+   HIP_TRY(ctx, hipGetLastError());
+
+   mark_stage(ctx, W, "seams");
+
+   return NFCGPU_OK;
+}
+
+/* The planes after the rounds when their walk ran beside: F.fs waits for the walk (planesJoin; the guard is disarmed), the chunks
+ * whose start state changed under it are listed into ctx->wPlaneChunks and counted (a host wait), and walked again on F.fs.
+ * Sets A.planes; A.planesStale is done with. */
+int front_planes_again(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F, PlanesGuard &planesGuard)
+{
+   const hipStream_t fs = F.fs;
+   NfcScanArgs &A = W.A;
+   const NfcScanParams &sp = W.sp;
+   const uint32_t nChunks = W.nChunks;
+   const bool debugStages = W.debugStages;
+   const NfcConfig *dCfg = W.dCfg;
+   uint32_t *counters = W.counters;
+   int rc;
+
+   /* the walk over all chunks has run beside the rounds: the chunks whose start state changed under it, again */
+   HIP_TRY(ctx, hipStreamWaitEvent(fs, ctx->planesJoin, 0));
+   planesGuard.running = false; /* (the main stream now waits for it) */
+
+   HIP_TRY(ctx, hipMemsetAsync(counters + 11, 0, 4, fs));
+   hipLaunchKernelGGL(nfc_planes_stale_kernel, dim3((nChunks + 255) / 256), dim3(256), 0, fs, A, (const NfcScanChunk *)ctx->wChunks.ptr, nChunks,
+                      (NfcScanChunk *)ctx->wPlaneChunks.ptr, counters + 11);
+   HIP_TRY(ctx, hipGetLastError());
+
+   uint32_t &again = ctx->frontHost[4];
+   HIP_TRY(ctx, hipMemcpyAsync(ctx->frontHost + 4, counters + 11, 4, hipMemcpyDeviceToHost, fs));
+   if ((rc = wait_front(ctx, F)))
+      return rc;
+
+   A.planes = (float *)ctx->wPlanes.ptr;
+   A.planesStale = nullptr;
+
+   if (debugStages)
+      std::fprintf(stderr, "[nfcgpu]    planes written beside the rounds; %u chunks of %u again\n", again, nChunks);
+
+   if (again)
+   {
+      NfcScanArgs P = A;
+      /* (a stored point per lane - 512 samples, from the points the rounds have left true -: a few thousand chunks a lane each
+       * would take as long as one chunk's walk, 12 ms, with the device all but idle) */
+      P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
+      P.nChunks = again;
+      P.planesPiece = NFC_SCAN_POINT;
+      P.planesPerChunk = sp.chunkSamples / NFC_SCAN_POINT;
+
+      ProfiledLaunch pp {nullptr, nullptr};
+      record_span(ctx, ctx->timedPlanes, pp, true, fs);
+      hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((uint32_t)(((uint64_t)again * P.planesPerChunk + NFC_LANES - 1) / NFC_LANES)), dim3(NFC_LANES), 0, fs, dCfg, P);
+      HIP_TRY(ctx, hipGetLastError());
+      record_span(ctx, ctx->timedPlanes, pp, false, fs);
+   }
+
+   mark_stage(ctx, W, "planes");
+
+   return NFCGPU_OK;
+}
+
+/* The planes after the rounds when no walk ran beside them: every chunk - of a small submission every piece - is listed on the
+ * host, uploaded and walked on F.fs, which is then waited for: the list is a local. Grows the planes' buffers (without the memory
+ * the submission is routed: front_no_memory) and sets A.planes. Reads W.jobs and W.chunks. */
+int front_planes_after(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F)
+{
+   const hipStream_t fs = F.fs;
+   NfcScanArgs &A = W.A;
+   const std::vector<NfcScanJob> &jobs = W.jobs;
+   const std::vector<NfcScanChunk> &chunks = W.chunks;
+   const uint32_t nJobs = W.nJobs;
+   const uint64_t totalSamples = W.totalSamples;
+   const NfcConfig *dCfg = W.dCfg;
+   int rc;
+
+   /* A small submission - one a caller waits for - is walked a lane per stored point instead of a lane per chunk: 512 samples
+    * instead of 4096 on the way of everything that follows (NFCGPU_PLANES_PIECE; a short capture: 1.1 -> 0.2 ms) */
+   const uint32_t piece = totalSamples <= (4u << 20) ? ctx->planesPiece / NFC_SCAN_POINT * NFC_SCAN_POINT : 0u;
+
+   std::vector<NfcScanChunk> all;
+
+   if (piece)
+   {
+      for (uint32_t j = 0; j < nJobs; j++)
+         for (uint32_t i = 0; i * piece < jobs[j].count; i++)
+            all.push_back(NfcScanChunk {j, i | NFC_CHUNK_REPAIR});
    }
    else
    {
-      rc = front(ctx->stream, false, false);
-      if (rc || routed)
-         return rc;
+      all = chunks;
+      for (NfcScanChunk &c: all)
+         c.index |= NFC_CHUNK_REPAIR;
    }
 
-   /* ---- the back: on the context's stream, the streams' own slots ---- */
+   const uint32_t nPlaneLanes = (uint32_t)all.size();
 
-   /* windows (again with more room when the guess was short) */
-   uint32_t nWindows = 0;
+   if ((rc = grow_planes(ctx, W, all.size(), false)))
+      return front_no_memory(ctx, W, F, rc);
+
+   HIP_TRY(ctx, hipMemcpyAsync(ctx->wPlaneChunks.ptr, all.data(), sizeof(NfcScanChunk) * all.size(), hipMemcpyHostToDevice, fs));
+
+   A.planes = (float *)ctx->wPlanes.ptr;
+
+   NfcScanArgs P = A;
+   P.chunks = (const NfcScanChunk *)ctx->wPlaneChunks.ptr;
+   P.nChunks = nPlaneLanes;
+   P.planesPiece = piece;
+
+   ProfiledLaunch pp {nullptr, nullptr};
+   record_span(ctx, ctx->timedPlanes, pp, true, fs);
+   hipLaunchKernelGGL(NFC_BY_LAYOUT(P.stride, nfc_scan_planes_kernel), dim3((nPlaneLanes + NFC_LANES - 1) / NFC_LANES), dim3(NFC_LANES), 0, fs, dCfg, P);
+   HIP_TRY(ctx, hipGetLastError());
+   record_span(ctx, ctx->timedPlanes, pp, false, fs);
+   if ((rc = wait_front(ctx, F)))
+      return rc; /* (the chunk list is a local) */
+
+   mark_stage(ctx, W, "planes");
+
+   return NFCGPU_OK;
+}
+
+/* The front of a submission: upload and scan, seam rounds until every chunk starts from the true state, the tile flags, the
+ * planes. Everything on F.fs but a planes walk beside the rounds (ctx->low); left early - an error, a submission routed
+ * elsewhere - the streams it used are waited for by the guards. */
+int front(nfcgpu_ctx *ctx, WindowedSubmission &W, const FrontPass &F)
+{
+   FrontGuard frontGuard {F.fs, F.beneath};
+   int rc;
+
+   if ((rc = front_scan(ctx, W, F)))
+      return rc;
+
+   /* The front-end planes (below) are a walk of every chunk from its verified start state: 69 GB of stores for config 5, 32 ms
+    * of a device that the rounds of second walks after the first leave nearly idle (a few thousand chunks each, as long as
+    * their longest chain). Round 5: for a large submission that walk is started on a stream of its own (lowest priority) as soon as the first round's
+    * second walks are queued - by then nine chunks in ten start from their true state -, the seam check and the envelope
+    * walks note every start state they rewrite from then on (NfcScanArgs::planesStale), and those chunks' planes are written
+    * again when the rounds are over. */
+   const bool planesBeside = ctx->planesBeside && ctx->low != nullptr && W.totalSamples > (4u << 20);
+   bool planesStarted = false;
+   PlanesGuard planesGuard {ctx, false};
+
+   if (planesBeside && ((rc = front_beside_room(ctx, W, F)) || W.routed))
+      return rc;
+
+   /* seams: chunks that did not start from the true state are walked again, a round at a time */
+   for (uint32_t round = 0;; round++)
+   {
+      uint32_t repairs = 0;
+
+      if (W.debugStages && W.debugLevel >= 4 && (rc = dump_seams(ctx, W, F, round)))
+         return rc;
+
+      if ((rc = front_seam_round(ctx, W, F, round, &repairs)) || W.routed)
+         return rc;
+
+      if (!repairs)
+         break;
+
+      if (planesBeside && round == 0)
+      {
+         if ((rc = front_planes_beside(ctx, W, F, planesGuard)))
+            return rc;
+         planesStarted = true;
+      }
+   }
+
+   if ((rc = front_tile_flags(ctx, W, F)))
+      return rc;
+
+   /* The wave decoder takes the front end's results per sample instead of walking it again: a second walk of every
+    * chunk from its verified start state (the repair form of the scan: no warm-up) writes them. */
+   rc = planesStarted ? front_planes_again(ctx, W, F, planesGuard) : front_planes_after(ctx, W, F);
+   if (rc || W.routed)
+      return rc;
+
+   frontGuard.armed = false;
+   return NFCGPU_OK;
+}
+
+/* The join of a front that ran under the pending tail: the tail is completed, the context's stream takes the front's work in
+ * (frontEvent), and the shadow states the front started from are compared with what the finish really left (a host wait on
+ * ctx->stream). The same but for zeroed edge times: the records are put right on ctx->stream. Anything else: the front again,
+ * on ctx->stream, from the slots (A.states). Counts pipelined_submissions, pipeline_zeroed_edges, pipeline_refronts. */
+int join_front(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   NfcScanArgs &A = W.A;
+   const uint32_t nJobs = W.nJobs;
+   int rc;
+
+   ctx->stats.pipelined_submissions++;
+
+   /* the tail, finish and any sequential fallback of its invalid jobs included; then the main stream takes the front's work in */
+   if ((rc = settle_tail(ctx)))
+   {
+      (void)hipStreamSynchronize(ctx->front);
+      return rc;
+   }
+
+   HIP_TRY(ctx, hipEventRecord(ctx->frontEvent, ctx->front));
+   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->frontEvent, 0));
+
+   /* exact or not taken: what the finish really left in the slots against the shadow states the front started from */
+   NfcShadowArgs S;
+   std::memset(&S, 0, sizeof(S));
+   S.jobs = A.jobs;
+   S.nJobs = nJobs;
+   S.real = ctx->dStates;
+   S.shadow = (NfcStreamState *)ctx->wShadow.ptr;
+   S.ctl = (uint32_t *)ctx->wShadowCtl.ptr;
+
+   S.points = A.points;
+   S.renameSeams = A.seams;
+   S.renameEdge = A.chunkEdge;
+
+   HIP_TRY(ctx, hipMemsetAsync(S.ctl, 0, 64, ctx->stream));
+   hipLaunchKernelGGL(nfc_shadow_compare_kernel, dim3((nJobs + 63) / 64), dim3(64), 0, ctx->stream, S);
+   HIP_TRY(ctx, hipGetLastError());
+   HIP_TRY(ctx, hipMemcpyAsync(ctx->tailHost + 16, S.ctl, 64, hipMemcpyDeviceToHost, ctx->stream));
+   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+   const uint32_t differ = ctx->tailHost[16], zeroed = ctx->tailHost[26];
+   A.states = ctx->dStates;
+
+   if (ctx->pipelineReport && !differ)
+      std::fprintf(stderr, "[nfcgpu] pipelined front: %u streams ended on a zeroed edge time (put right in the records), none differs otherwise\n", zeroed);
+
+   if (!differ)
+      ctx->stats.pipeline_zeroed_edges += zeroed;
+
+   if (zeroed && !differ)
+   {
+      /* (a carrier frame after the tracker last moved: NfcShadowArgs) */
+      hipLaunchKernelGGL(nfc_shadow_rename_kernel, dim3(nJobs), dim3(64), 0, ctx->stream, S);
+      HIP_TRY(ctx, hipGetLastError());
+   }
+
+   if (differ)
+   {
+      /* streams that did not end where their front-end records said (a stream the sequential kernels decoded, say): the front
+       * again, unpipelined, from the true state */
+      const uint32_t *f = ctx->tailHost + 16;
+      ctx->stats.pipeline_refronts += differ;
+
+      if (ctx->pipelineReport)
+         std::fprintf(stderr, "[nfcgpu] pipelined front redone: %u streams differ from their shadow state otherwise than by a zeroed edge time (clock %u, pulse counter %u, envelope %u, n1 %u, deviation %u, average %u, "
+                              "edge peak %u, edge time %u, carrier zone %u)\n", f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9]);
+
+      return front(ctx, W, FrontPass {ctx->stream, false, true});
+   }
+
+   return NFCGPU_OK;
+}
+
+/* ---- the back: on the context's stream, the streams' own slots ---- */
+
+/* records per lane slot (carry lanes, final lanes, one per window); ring and frame-assembly storage per carry lane,
+ * final lane and per lane of the persistent waves that run the windows */
+int grow_lanes(nfcgpu_ctx *ctx, const WindowedSubmission &W, uint32_t lanesWanted)
+{
+   const size_t storageLanes = (size_t)W.firstWindowSlot; /* (a speculative window's rings live in LDS; one that runs to the end leaves a copy in the save area) */
+   const size_t lanes = ((size_t)lanesWanted + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
+   int r;
+   if ((r = grow(ctx, ctx->wWindows, sizeof(NfcWindow) * lanes)) || (r = grow(ctx, ctx->wWorks, sizeof(NfcWork) * lanes)) ||
+       (r = grow(ctx, ctx->vStates, sizeof(NfcStreamState) * lanes)) || (r = grow(ctx, ctx->vCold, sizeof(NfcStreamCold) * lanes)) ||
+       (r = grow(ctx, ctx->wRunList, 4 * lanes)) ||
+       (r = grow(ctx, ctx->vRings, sizeof(float) * (size_t)kRingBlockFloats * (storageLanes / NFC_LANES))) ||
+       (r = grow(ctx, ctx->vBytes, (size_t)NFC_STREAM_BYTES * storageLanes)))
+      return r;
+   return NFCGPU_OK;
+}
+
+/* The lane buffers: room for a first guess at the windows, or what an earlier, larger submission has left. Sets A.windows, A.works,
+ * A.runList and A.windowRoom; without the memory the submission is routed. Queues nothing. */
+int back_lane_buffers(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   NfcScanArgs &A = W.A;
+   const uint32_t nJobs = W.nJobs, firstWindowSlot = W.firstWindowSlot;
+   const uint64_t totalSamples = W.totalSamples;
+   int rc;
 
    /* lanes: a first guess (one window per 8192 samples); the window kernel reports what it needs */
    uint32_t room = (uint32_t)(totalSamples / 8192) + 2 * nJobs + 64;
-
-   /* records per lane slot (carry lanes, final lanes, one per window); ring and frame-assembly storage per carry lane,
-    * final lane and per lane of the persistent waves that run the windows */
-   const size_t storageLanes = (size_t)firstWindowSlot; /* (a speculative window's rings live in LDS; one that runs to the end leaves a copy in the save area) */
-
-   auto growLanes = [&](uint32_t lanesWanted) -> int {
-      const size_t lanes = ((size_t)lanesWanted + NFC_LANES - 1) / NFC_LANES * NFC_LANES;
-      int r;
-      if ((r = grow(ctx, ctx->wWindows, sizeof(NfcWindow) * lanes)) || (r = grow(ctx, ctx->wWorks, sizeof(NfcWork) * lanes)) ||
-          (r = grow(ctx, ctx->vStates, sizeof(NfcStreamState) * lanes)) || (r = grow(ctx, ctx->vCold, sizeof(NfcStreamCold) * lanes)) ||
-          (r = grow(ctx, ctx->wRunList, 4 * lanes)) ||
-          (r = grow(ctx, ctx->vRings, sizeof(float) * (size_t)kRingBlockFloats * (storageLanes / NFC_LANES))) ||
-          (r = grow(ctx, ctx->vBytes, (size_t)NFC_STREAM_BYTES * storageLanes)))
-         return r;
-      return NFCGPU_OK;
-   };
 
    /* is there room already from an earlier, larger submission? */
    {
@@ -2556,8 +2758,23 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
          room = (uint32_t)(have - firstWindowSlot - NFC_LANES);
    }
 
-   if ((rc = growLanes(firstWindowSlot + room)))
-      return withoutTheMemory(rc);
+   if ((rc = grow_lanes(ctx, W, firstWindowSlot + room)))
+      return without_the_memory(ctx, W, rc);
+
+   A.windows = (NfcWindow *)ctx->wWindows.ptr;
+   A.works = (NfcWork *)ctx->wWorks.ptr;
+   A.windowRoom = room;
+   A.runList = (uint32_t *)ctx->wRunList.ptr;
+   return NFCGPU_OK;
+}
+
+/* The staging sink of the lanes' frame records, its control words cleared on ctx->stream, and the save area of lanes that run to
+ * the end of the submission (A.saveRings, A.saveBytes, A.saveRoom). Without the memory the submission is routed. */
+int back_sink_and_save(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   NfcScanArgs &A = W.A;
+   const uint32_t nJobs = W.nJobs;
+   int rc;
 
    /* staging sink for the lanes' chained frame records (lanes that turn out not to be live write theirs too): room
     * for four times the frame sink, at least 64 MiB; what does not fit is reported as dropped like any overflow */
@@ -2568,34 +2785,38 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
       if (staging > 0xFFFFFFF0ull * 4ull)
          staging = 0xFFFFFFF0ull * 4ull;
       if ((rc = grow(ctx, ctx->vSink, staging)) || (rc = grow(ctx, ctx->vSinkCtl, 16)))
-         return withoutTheMemory(rc);
+         return without_the_memory(ctx, W, rc);
    }
 
    HIP_TRY(ctx, hipMemsetAsync(ctx->vSinkCtl.ptr, 0, 16, ctx->stream));
-
-   A.windows = (NfcWindow *)ctx->wWindows.ptr;
-   A.works = (NfcWork *)ctx->wWorks.ptr;
-   A.windowRoom = room;
-   A.runList = (uint32_t *)ctx->wRunList.ptr;
 
    /* save area for lanes that run to the end of the submission (nfc_scan_launch.h): a few per stream */
    {
       const uint32_t saveRoom = 2 * nJobs + 1024;
       if ((rc = grow(ctx, ctx->vSaveRings, sizeof(float) * (size_t)(kRingBlockFloats / NFC_LANES) * saveRoom)) ||
           (rc = grow(ctx, ctx->vSaveBytes, (size_t)NFC_STREAM_BYTES * saveRoom)))
-         return withoutTheMemory(rc);
+         return without_the_memory(ctx, W, rc);
 
       A.saveRings = (float *)ctx->vSaveRings.ptr;
       A.saveBytes = (uint8_t *)ctx->vSaveBytes.ptr;
-      A.saveNext = counters + 8;
       A.saveRoom = saveRoom;
    }
 
-   /* The shadow states a submission that continues these streams may start its front from while this one's tail is pending: the
-    * slot as the front found it, its front-end fields set from the end of the last chunk - the front end is a function of the
-    * samples, and once the rounds are over that end is the true one - the way nfc_window_lane turns a point into state. (Nobody
-    * reads the shadows of the submission before any more: its successor's front - this one - has been joined.) */
-   const bool shadows = ctx->pipeline && !ctx->inBlocks && !debugStages && ctx->deferOK && !ctx->noSecondSet && ctx->front != nullptr;
+   return NFCGPU_OK;
+}
+
+/* The shadow states a submission that continues these streams may start its front from while this one's tail is pending: the
+ * slot as the front found it, its front-end fields set from the end of the last chunk - the front end is a function of the
+ * samples, and once the rounds are over that end is the true one - the way nfc_window_lane turns a point into state. (Nobody
+ * reads the shadows of the submission before any more: its successor's front - this one - has been joined.)
+ *
+ * Sets W.shadows; the first time grows ctx->wShadow / wShadowCtl (a device that cannot give them: noSecondSet). The kernel runs on
+ * ctx->stream and reads the slots and the seam records. */
+int back_shadow_states(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   const NfcScanArgs &A = W.A;
+   const uint32_t nJobs = W.nJobs;
+   const bool shadows = W.shadows = ctx->pipeline && !ctx->inBlocks && !W.debugStages && ctx->deferOK && !ctx->noSecondSet && ctx->front != nullptr;
 
    if (shadows && !ctx->wShadow.ptr)
    {
@@ -2623,6 +2844,20 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
       HIP_TRY(ctx, hipGetLastError());
    }
 
+   return NFCGPU_OK;
+}
+
+/* Window placement on ctx->stream, a host wait for the count (W.nWindows); again with more room when the guess was short. May
+ * grow the lane buffers and set A's pointers to them anew; without the memory the submission is routed. */
+int back_place_windows(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   NfcScanArgs &A = W.A;
+   const uint32_t nJobs = W.nJobs, firstWindowSlot = W.firstWindowSlot;
+   uint32_t *counters = W.counters;
+   uint32_t &nWindows = W.nWindows;
+   uint32_t room = A.windowRoom;
+   int rc;
+
    for (int attempt = 0; attempt < 2; attempt++)
    {
       hipLaunchKernelGGL(nfc_windows_kernel, dim3(nJobs), dim3(64), 0, ctx->stream, A);
@@ -2634,17 +2869,31 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
          break;
 
       room = nWindows + NFC_LANES;
-      if ((rc = growLanes(firstWindowSlot + room)))
-         return withoutTheMemory(rc);
+      if ((rc = grow_lanes(ctx, W, firstWindowSlot + room)))
+         return without_the_memory(ctx, W, rc);
 
       A.windows = (NfcWindow *)ctx->wWindows.ptr;
       A.works = (NfcWork *)ctx->wWorks.ptr;
-         A.runList = (uint32_t *)ctx->wRunList.ptr;
+      A.runList = (uint32_t *)ctx->wRunList.ptr;
       A.windowRoom = room;
       HIP_TRY(ctx, hipMemsetAsync(counters, 0, 4, ctx->stream));
    }
 
-   mark("windows");
+   mark_stage(ctx, W, "windows");
+
+   return NFCGPU_OK;
+}
+
+/* The lanes' launch record, the carry lanes on ctx->stream and the hand-off: a WindowedTail takes what is left of the submission,
+ * is advanced to the end of the first pass and the chain kernel behind it (host waits) and then either stays pending on the
+ * context - the rule is below - or is completed here. */
+int back_lanes_and_tail(nfcgpu_ctx *ctx, WindowedSubmission &W)
+{
+   const NfcScanArgs &A = W.A;
+   const uint32_t nJobs = W.nJobs, nWindows = W.nWindows;
+   uint32_t *counters = W.counters;
+   const bool shadows = W.shadows;
+   int rc;
 
    NfcLaunch real = base_launch(ctx);
 
@@ -2664,7 +2913,7 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
    lanes.windows = (NfcWindow *)ctx->wWindows.ptr;
    lanes.jobs = (const NfcScanJob *)ctx->wJobs.ptr;
    lanes.laneStats = counters + 4;
-   lanes.uniformStride = stride;
+   lanes.uniformStride = W.stride;
 
    /* lanes */
    hipLaunchKernelGGL(nfc_carry_lanes_kernel, dim3(nJobs), dim3(NFC_LANES), 0, ctx->stream, A, real, lanes, 0u);
@@ -2672,28 +2921,27 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
 
    const uint32_t windowBlocks = (nWindows + NFC_LANES - 1) / NFC_LANES;
 
-
    WindowedTail *T = new (std::nothrow) WindowedTail();
    if (!T)
       return fail(ctx, NFCGPU_ENOMEM, "out of host memory");
 
-   T->config = config;
-   T->stride = stride;
-   T->items = items;
+   T->config = W.config;
+   T->stride = W.stride;
+   T->items = W.items;
    T->A = A;
    T->real = real;
    T->lanes = lanes;
-   T->dCfg = dCfg;
+   T->dCfg = W.dCfg;
    T->counters = counters;
    T->dJobs = ctx->wJobs.ptr;
    T->nJobs = nJobs;
    T->nWindows = nWindows;
    T->windowBlocks = windowBlocks;
-   T->firstWindowSlot = firstWindowSlot;
-   T->finalLaneSlot = finalLaneSlot;
-   T->totalSamples = totalSamples;
-   T->debugStages = debugStages;
-   T->stageBegan = stageBegan;
+   T->firstWindowSlot = W.firstWindowSlot;
+   T->finalLaneSlot = W.finalLaneSlot;
+   T->totalSamples = W.totalSamples;
+   T->debugStages = W.debugStages;
+   T->stageBegan = W.stageBegan;
    T->ready = take_event(ctx);
    record_span(ctx, ctx->timedWindow, T->pw, true);
 
@@ -2722,6 +2970,61 @@ int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedIte
    }
 
    return settle_tail(ctx);
+}
+
+/* One submission of `items` (all of configuration `config`, `stride` floats per sample, data resident on the device)
+ * through scan -> windows -> windowed decode -> chain -> finish; streams the path cannot vouch for (samples off the
+ * int16 grid, a seam that did not verify, no settled chain) are then decoded sequentially from their untouched state.
+ *
+ * It has a front - tables, scan, seam rounds, planes, tile flags: a function of the samples and of the front-end state the
+ * streams start from - and a back: windows, decode passes, chain, finish. The back's own end (WindowedTail) may stay pending
+ * when the call returns; a submission that continues the same streams then runs its front under it, on ctx->front, from the
+ * shadow states the pending submission's back has left for it (nfc_shadow_kernel), and once the tail is done has the shadows
+ * compared with what the finish really wrote: a front that started from anything else is walked again from the true state.
+ *
+ * In the order of the stages above: plan, buffers, front - or front under the tail, then the join -, back, tail. */
+int run_windowed(nfcgpu_ctx *ctx, uint32_t config, const std::vector<WindowedItem> &items, uint32_t stride)
+{
+   const auto entered = std::chrono::steady_clock::now();
+   const char *debug = std::getenv("NFCGPU_WINDOW_DEBUG");
+   WindowedSubmission W {config, stride, items, ctx->configs[config], (uint32_t)items.size(), debug != nullptr, debug ? std::atoi(debug) : 0, entered};
+   int rc;
+
+   if (ctx->tail)
+   {
+      W.under = !W.debugStages && may_overlap(ctx, config, items);
+
+      if (!W.under && (rc = settle_tail(ctx)))
+         return rc;
+   }
+
+   if (W.debugStages && ctx->pipeline && !ctx->inBlocks)
+      std::fprintf(stderr, "[nfcgpu] the stage log is of unpipelined submissions: with NFCGPU_WINDOW_DEBUG set every submission is complete when its call returns\n");
+
+   plan_scan_params(ctx, W);
+   plan_tables(ctx, W);
+
+   if (W.under && (rc = take_second_set(ctx, W)))
+      return rc;
+
+   if (!W.under && (rc = grow_front(ctx, W, false)))
+      return without_the_memory(ctx, W, rc);
+
+   fill_scan_args(ctx, W);
+
+   if (W.under)
+   {
+      if ((rc = front(ctx, W, FrontPass {ctx->front, true, false})) || W.routed || (rc = join_front(ctx, W)) || W.routed)
+         return rc;
+   }
+   else if ((rc = front(ctx, W, FrontPass {ctx->stream, false, false})) || W.routed)
+      return rc;
+
+   if ((rc = back_lane_buffers(ctx, W)) || W.routed || (rc = back_sink_and_save(ctx, W)) || W.routed || (rc = back_shadow_states(ctx, W)) ||
+       (rc = back_place_windows(ctx, W)) || W.routed)
+      return rc;
+
+   return back_lanes_and_tail(ctx, W);
 }
 
 

@@ -1,9 +1,11 @@
-"""Pipelined submissions (the front of a submission under the tail of the one before: run_windowed, csrc/nfcgpu.hip) against
+"""Pipelined submissions (the front of a submission under the tail of the one before: front / join_front, csrc/nfcgpu.hip) against
 the parent commit: bench.py of a built checkout of the parent and of this tree run alternately, parent first, for the default
 command and for `--gpus 1 --steps 20 --warmup 5`; and, from rocprofv3 kernel traces of `bench.py --steps 4 --warmup 2`, the
 front and the tail of a step and what runs between the end of a step's first decode pass and its nfc_finish_kernel.
 
-  python profiles/tools/bench_pipeline.py --parent-tree DIR [--runs 3] [--outputs] [--points] [--trace-parent CSV] [--trace CSV] [--out FILE]
+  python profiles/tools/bench_pipeline.py --parent-tree DIR [--runs 3] [--commands default,steps20] [--outputs] [--points] [--trace-parent CSV] [--trace CSV] [--out FILE]
+
+--commands: which of the two commands (a visit too short for both takes one at a time; the files are put together afterwards).
 
 --outputs: `bench.py --dump-outputs` for both commands on both trees, frames.npy and frame_payload.npy held against each other
 with numpy.array_equal, frames_decoded_rank0 and frames_dropped beside them, and the pipeline counters of this tree per step
@@ -33,6 +35,7 @@ def bench(tree, extra):
         raise SystemExit("bench.py failed in %s: %s" % (tree, run.stderr[-2000:]))
     line = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])
     cfg = line.get("config", {})
+    print("bench.py %s in %s: %s ms per step" % (" ".join(extra), tree, cfg.get("ms_per_step")), file=sys.stderr, flush=True)
     return {"value": line["value"], "ms_per_step": cfg.get("ms_per_step"), "time_parallel": cfg.get("time_parallel"),
             "frames_decoded_rank0": cfg.get("frames_decoded_rank0"), "frames_dropped": cfg.get("frames_dropped")}
 
@@ -130,6 +133,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree", default=None)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--commands", default=",".join(COMMANDS))
     ap.add_argument("--outputs", action="store_true")
     ap.add_argument("--points", action="store_true")
     ap.add_argument("--trace-parent", default=None)
@@ -137,10 +141,11 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pipelined_submissions.json"))
     args = ap.parse_args()
 
+    commands = {name: COMMANDS[name] for name in args.commands.split(",")}
     result = {"op": "front of submission k+1 under the tail of submission k (pipelined submissions) against the parent commit"}
 
     if args.parent_tree:
-        for name, extra in COMMANDS.items():
+        for name, extra in commands.items():
             runs = {"parent": [], "this": []}
             for _ in range(args.runs):
                 runs["parent"].append(bench(args.parent_tree, extra))
@@ -150,7 +155,7 @@ def main():
                             "this": {k: spread(runs["this"], k) for k in ("value", "ms_per_step")}}
 
     if args.parent_tree and args.outputs:
-        result["outputs"] = {name: outputs(args.parent_tree, extra) for name, extra in COMMANDS.items()}
+        result["outputs"] = {name: outputs(args.parent_tree, extra) for name, extra in commands.items()}
         result["counters_headline_shape"] = counters()
 
     if args.parent_tree and args.points:
