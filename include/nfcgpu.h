@@ -317,6 +317,71 @@ int nfcgpu_record(nfcgpu_ctx *ctx, const float *in, uint64_t in_pitch_bytes, uin
                   uint32_t stride, uint32_t mode, int16_t *out, uint64_t out_pitch_bytes,
                   nfcgpu_record_levels *levels /* may be NULL */, uint32_t location);
 
+/* The signal debug tap: what the decoder's front end makes of every sample, as planes of floats - the values
+ * NfcDecoderStatus::nextSample (NfcTech.cpp:28-105) hands to NfcSignalDebug with setEnableDebug(true) (:94-102, channels 0-3 of
+ * radio-debug-*.wav: samplingValue, filteredValue, meanDeviation, signalAverage), and the two the detectors gate on, the envelope
+ * (:39-53, against the power threshold) and the modulation depth (:74, against min / max_modulation_depth).
+ *
+ * Buffer b is n_samples samples of `stride` (1 magnitude, 2 interleaved I/Q) and `format` (NFCGPU_FMT_*) at in + b * in_pitch_bytes;
+ * `in` and in_pitch_bytes are multiples of a sample (stride * 4 bytes of NFCGPU_FMT_F32, stride * 2 of NFCGPU_FMT_I16), as for
+ * the _fmt submit calls, and samples are loaded exactly as those load them. The k-th channel selected in params->channels, in bit
+ * order, is written as n_samples floats at out + b * out_pitch_bytes + k * plane_pitch_bytes (planar; `out` 4-byte aligned,
+ * both pitches multiples of 16, plane_pitch_bytes >= 4 * n_samples, out_pitch_bytes at least the planes of a buffer when there
+ * is more than one buffer; bytes beyond a plane's n_samples floats are left alone). state_in / state_out are n_buffers
+ * records (4-byte aligned). `location` applies to in, out, state_in and state_out; `report` is host memory. The call returns
+ * when `out` is complete. n_samples == 0 or n_buffers == 0 is success and writes no planes; state_out is then state_in.
+ *
+ * Every float written is the value the device step machine produces when it is given the buffer sample by sample from
+ * state_in - per sample ++clock, ++pulse_filter, the front end, the depth - bit for bit (a NaN where that walk gives a NaN, such
+ * as the depth of a first sample of 0), and state_out is that walk's state behind the last sample. The buffers are cut into
+ * chunks that are walked side by side, each from a guess some samples ahead of it, and every chunk whose walk did not start in
+ * the very state the chunk before it ended in is walked again from there, round after round, until none is left: results
+ * do not depend on chunk_samples, warm_samples, n_buffers, where the rows lie, or the run. report: chunks in all, rounds of
+ * second walks, chunks walked twice.
+ *
+ * NFCGPU_EINVAL: a NULL or misaligned pointer, channels 0 or with unknown bits, a stride, format, location, pitch or chunk_samples
+ * that is not as above, reserved fields that are not zero, sample_rate 0, more than 2^32 - 1 chunks. NFCGPU_ERATE: a sample rate
+ * the decoder refuses.
+ *
+ * Alignment with the decoder. nfcgpu_stream_tap_state completes what is pending on the context and gives the front-end state the
+ * stream's next buffer at its stored rate will start from: that of a stream just opened before its first buffer, after
+ * nfcgpu_stream_reset the restarted clock with pulse filter, envelope, filter, deviation and average carried on. Tapping a
+ * buffer from that state and then submitting the same buffer gives planes whose index i is the sample the frames' sample_start /
+ * sample_end count: sample i of the buffer has the clock state.clock + 1 + i (32-bit), the number a frame carries. */
+#define NFCGPU_TAP_VALUE     0x01u /* samplingValue: the sample as the decoder takes it (stride 2: nfc_iq_magnitude of the pair) */
+#define NFCGPU_TAP_FILTERED  0x02u /* filteredValue, NfcTech.cpp:55-62 */
+#define NFCGPU_TAP_DEVIATION 0x04u /* meanDeviation, :65 */
+#define NFCGPU_TAP_AVERAGE   0x08u /* signalAverage, :68 */
+#define NFCGPU_TAP_ENVELOPE  0x10u /* signalEnvelope after this sample's update, :39-53 */
+#define NFCGPU_TAP_DEPTH     0x20u /* modulateDepth, :74 */
+
+typedef struct nfcgpu_tap_state {   /* 32 bytes: what the front end carries from one sample to the next */
+   uint32_t clock, pulse_filter;
+   float envelope, filter_n1, deviation, average;
+   uint32_t reserved[2];            /* zero */
+} nfcgpu_tap_state;
+
+typedef struct nfcgpu_tap_params {
+   uint32_t sample_rate;   /* Hz: the weights and the elementary time unit are the decoder's for this rate (NfcDecoder.cpp:295-360) */
+   uint32_t channels;      /* NFCGPU_TAP_* mask, not 0 */
+   uint32_t chunk_samples; /* 0 = the library's choice; else a multiple of 64: samples one walker takes */
+   uint32_t warm_samples;  /* used with chunk_samples != 0: samples a walker runs before its chunk from a guessed state (0 allowed) */
+   uint32_t reserved[4];   /* zero */
+} nfcgpu_tap_params;
+
+typedef struct nfcgpu_tap_report { uint32_t chunks, rounds, rewalked_chunks, reserved; } nfcgpu_tap_report;
+
+void nfcgpu_tap_state_init(nfcgpu_tap_state *s);   /* a stream just opened: clock 0xFFFFFFFF, the rest 0 */
+
+int nfcgpu_signal_tap(nfcgpu_ctx *ctx, const void *in, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_samples,
+                      uint32_t stride, uint32_t format, const nfcgpu_tap_params *params,
+                      const nfcgpu_tap_state *state_in /* n_buffers, NULL = all freshly opened */,
+                      float *out, uint64_t out_pitch_bytes, uint64_t plane_pitch_bytes,
+                      nfcgpu_tap_state *state_out /* n_buffers, may be NULL */,
+                      nfcgpu_tap_report *report /* host memory, may be NULL */, uint32_t location);
+
+int nfcgpu_stream_tap_state(nfcgpu_ctx *ctx, uint32_t stream_id, nfcgpu_tap_state *state /* host */);
+
 /* Capture files as hw::RecordDevice writes them (RecordDevice.cpp:493-546, structures :53-100), host only, no context and
  * no device: a 92-byte header - RIFF / WAVE; "fmt " (16: PCM 1, channels, rate, byte rate, block align, 16 bits); "META" (40:
  * "meta", epoch = stream_time, keys[8], the first `channels` taken from `keys`, NULL = zeros); "data" - then the samples,

@@ -29,6 +29,15 @@
 #include "nfc_spectrum.hpp"
 #include "nfc_sample.hpp"
 #include "nfc_record.hpp"
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+/* (the twins of the tap kernels walk the decoder's step machine: nfc_core.hpp as the CPU builds of tests/hostsim compile it) */
+#define NFC_DEV static inline
+static inline uint32_t tap_twin_add(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p += v; return old; }
+#define NFC_ATOMIC_ADD(ptr, value) tap_twin_add((ptr), (value))
+#define NFC_ANY(predicate) (predicate)
+#include "nfc_core.hpp"
+#endif
+#include "nfc_tap.hpp"
 
 __global__ void nfc_demod_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
 __global__ void nfc_demod_exact_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
@@ -235,6 +244,78 @@ NFC_RECORD_KERNEL(nfc_record_kernel_iq_levels, 2, NFC_RECORD_SAME, true)
 NFC_RECORD_KERNEL(nfc_record_kernel_magnitude, 2, NFC_RECORD_MAGNITUDE, false)
 NFC_RECORD_KERNEL(nfc_record_kernel_magnitude_levels, 2, NFC_RECORD_MAGNITUDE, true)
 #undef NFC_RECORD_KERNEL
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+/* The test build's twins of the tap kernels (nfc_tap.hip): the groups, tiles and lanes of nfc_tap.hpp as loops, the end of a loop
+ * over the lanes where the device has a barrier, a plain minimum where it has an atomic one. */
+void nfc_tap_walk_kernel(NfcTapArgs A, NfcConfig cfg)
+{
+   static float tiles[(1 + NfcTapShape::kPlanes) * NfcTapShape::kPlaneFloats];
+   float *tileIn = tiles, *tileOut = tiles + NfcTapShape::kPlaneFloats;
+   NfcTapWalker walkers[NfcTapShape::kWalkers];
+   NfcTapState s[NfcTapShape::kWalkers], start[NfcTapShape::kWalkers];
+
+   const uint32_t planes = nfc_tap_planes(A.mask);
+   const uint64_t groups = (A.walkers + NfcTapShape::kWalkers - 1) / NfcTapShape::kWalkers;
+
+   for (uint64_t group = 0; group < groups; group++)
+   {
+      for (uint32_t lane = 0; lane < NfcTapShape::kWalkers; lane++)
+      {
+         walkers[lane] = nfc_tap_walker(A, group * NfcTapShape::kWalkers + lane);
+         s[lane] = walkers[lane].total ? nfc_tap_begin(A, walkers[lane]) : nfc_tap_fresh();
+         start[lane] = s[lane];
+      }
+
+      for (uint32_t tile = 0; tile < A.tiles; tile++)
+      {
+         for (uint32_t lane = 0; lane < NfcTapShape::kWalkers; lane++)
+            nfc_tap_fetch(A, walkers, tile, lane, tileIn);
+         for (uint32_t lane = 0; lane < NfcTapShape::kWalkers; lane++)
+            nfc_tap_walk(A, cfg, walkers[lane], tile, lane, s[lane], start[lane], tileIn, tileOut);
+         for (uint32_t lane = 0; lane < NfcTapShape::kWalkers; lane++)
+            nfc_tap_store(A, walkers, tile, lane, planes, tileOut);
+      }
+
+      for (uint32_t lane = 0; lane < NfcTapShape::kWalkers; lane++)
+         nfc_tap_end(A, walkers[lane], start[lane], s[lane]);
+   }
+}
+
+void nfc_tap_seam_kernel(NfcTapArgs A)
+{
+   for (uint64_t id = 0; id < (uint64_t)A.nBuffers * A.chunksPerBuffer; id++)
+   {
+      uint32_t &next = A.next[id / A.chunksPerBuffer];
+      const uint32_t k = (uint32_t)(id % A.chunksPerBuffer);
+
+      if (nfc_tap_seam_open(A, (uint32_t)id) && k < next)
+         next = k;
+   }
+}
+
+void nfc_tap_list_kernel(NfcTapArgs A)
+{
+   for (uint32_t b = 0; b < A.nBuffers; b++)
+   {
+      uint32_t id;
+
+      if (nfc_tap_seam_close(A, b, id))
+         A.listOut[A.count[0]++] = id;
+   }
+}
+
+void nfc_tap_finish_kernel(NfcTapArgs A)
+{
+   for (uint32_t b = 0; b < A.nBuffers; b++)
+      nfc_tap_finish(A, b);
+}
+#else
+__global__ void nfc_tap_walk_kernel(NfcTapArgs A, NfcConfig cfg);
+__global__ void nfc_tap_seam_kernel(NfcTapArgs A);
+__global__ void nfc_tap_list_kernel(NfcTapArgs A);
+__global__ void nfc_tap_finish_kernel(NfcTapArgs A);
+#endif
 
 /* ---- helper kernels of pipelined submissions (run_windowed): a thread per stream of the submission ----
  * The front of a submission (scan, seam rounds, planes) reads of a stream's slot the front-end state its first chunk starts from:
@@ -620,6 +701,11 @@ struct nfcgpu_ctx
    /* nfcgpu_record: one partial per segment of every buffer of a call (device), grown on demand, kept */
    void *recordPartials = nullptr;
    size_t recordPartialsBytes = 0;
+   /* nfcgpu_signal_tap: the walkers' start and end states, the frontiers and the list of a call (device), grown on demand, kept;
+    * the length of a round's list as the host reads it (pinned) */
+   void *tapScratch = nullptr;
+   size_t tapScratchBytes = 0;
+   uint32_t *tapCount = nullptr;
 };
 
 namespace {
@@ -3593,6 +3679,10 @@ int nfcgpu_shutdown(nfcgpu_ctx *ctx)
       (void)hipFree(t.d);
    if (ctx->recordPartials)
       (void)hipFree(ctx->recordPartials);
+   if (ctx->tapScratch)
+      (void)hipFree(ctx->tapScratch);
+   if (ctx->tapCount)
+      (void)hipHostFree(ctx->tapCount);
    for (nfcgpu_ctx::StageSlot &slot: ctx->stage)
    {
       if (slot.d)
@@ -4585,6 +4675,366 @@ int nfcgpu_record(nfcgpu_ctx *ctx, const float *in, uint64_t inPitch, uint32_t n
       return fail(ctx, NFCGPU_EHIP, "record", err);
 
    return NFCGPU_OK;
+}
+
+/* ---- nfcgpu_signal_tap: the front end's per-sample signals (NfcDecoderStatus::nextSample with setEnableDebug(true),
+ * NfcTech.cpp:28-105) for buffers wherever they lie, cut in time (nfc_tap.hpp) ---- */
+
+static_assert(sizeof(nfcgpu_tap_state) == sizeof(NfcTapRecord) && sizeof(NfcTapRecord) == 32 && sizeof(NfcTapState) == 24, "a tap state is 32 bytes, 24 of them used");
+static_assert(NFCGPU_TAP_VALUE == NFC_TAP_VALUE && NFCGPU_TAP_FILTERED == NFC_TAP_FILTERED && NFCGPU_TAP_DEVIATION == NFC_TAP_DEVIATION &&
+              NFCGPU_TAP_AVERAGE == NFC_TAP_AVERAGE && NFCGPU_TAP_ENVELOPE == NFC_TAP_ENVELOPE && NFCGPU_TAP_DEPTH == NFC_TAP_DEPTH, "the planes of the header");
+
+/* The library's choice of chunk and warm-up (the section on the tap). Warm-up: 4096 samples at 10 MS/s, as many time
+ * constants of the slowest recurrence (the average, 1 / meanW1 samples) at any rate. Chunk: what cuts the call into about kTapWalkers
+ * walkers, a wave for every SIMD of the chip, and no shorter than kTapMinChunk; a call of many buffers, which fills waves whatever
+ * the chunk, takes chunks of at least twice the warm-up; never more than a buffer. */
+constexpr uint64_t kTapWalkers = 65536;
+constexpr uint64_t kTapMinChunk = 256;
+constexpr uint32_t kTapManyBuffers = 1024;
+constexpr uint32_t kTapMaxChunk = 0xFFFFFFC0u;
+
+static uint32_t tap_default_warm(uint32_t sampleRate)
+{
+   uint64_t w = ((uint64_t)sampleRate * 4096u + 9999999u) / 10000000u;
+   w = (w + 63u) & ~(uint64_t)63;
+   return (uint32_t)(w < 64u ? 64u : (w > 8192u ? 8192u : w));
+}
+
+static uint32_t tap_default_chunk(uint32_t nBuffers, uint32_t n, uint32_t warm)
+{
+   uint64_t c = (uint64_t)nBuffers * n / kTapWalkers;
+
+   if (c < kTapMinChunk)
+      c = kTapMinChunk;
+   if (nBuffers >= kTapManyBuffers && c < 2ull * warm)
+      c = 2ull * warm;
+
+   const uint64_t whole = ((uint64_t)n + 63u) & ~(uint64_t)63;
+
+   if (c > whole)
+      c = whole;
+   c = (c + 63u) & ~(uint64_t)63;
+   return c > kTapMaxChunk ? kTapMaxChunk : (uint32_t)c;
+}
+
+void nfcgpu_tap_state_init(nfcgpu_tap_state *s)
+{
+   if (!s)
+      return;
+   std::memset(s, 0, sizeof(*s));
+   s->clock = 0xFFFFFFFFu;
+}
+
+int nfcgpu_signal_tap(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, uint32_t stride, uint32_t format,
+                      const nfcgpu_tap_params *params, const nfcgpu_tap_state *stateIn, float *out, uint64_t outPitch, uint64_t planePitch,
+                      nfcgpu_tap_state *stateOut, nfcgpu_tap_report *report, uint32_t location)
+{
+   SETTLE_FIRST(ctx);
+
+   if (!ctx)
+      return NFCGPU_EINVAL;
+   if (!params)
+      return fail(ctx, NFCGPU_EINVAL, "tap: params is NULL");
+   if (params->channels == 0 || (params->channels & ~NFC_TAP_ALL))
+      return fail(ctx, NFCGPU_EINVAL, "tap: channels is 0 or has bits that are no NFCGPU_TAP_* channel");
+   if (params->reserved[0] | params->reserved[1] | params->reserved[2] | params->reserved[3])
+      return fail(ctx, NFCGPU_EINVAL, "tap: reserved fields of params are not zero");
+   if (stride != 1 && stride != 2)
+      return fail(ctx, NFCGPU_EINVAL, "tap: stride is neither 1 nor 2");
+   if (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16)
+      return fail(ctx, NFCGPU_EINVAL, "tap: unknown format");
+   if (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE)
+      return fail(ctx, NFCGPU_EINVAL, "tap: unknown location");
+   if (params->chunk_samples % 64u)
+      return fail(ctx, NFCGPU_EINVAL, "tap: chunk_samples is not a multiple of 64");
+
+   const uint32_t layout = stride | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u);
+   const uint64_t sampleBytes = nfc_sample_bytes(layout);
+   const uint32_t planes = nfc_tap_planes(params->channels);
+   const uint64_t planeBytes = (uint64_t)n * 4u;
+
+   if (!in || ((uintptr_t)in % sampleBytes))
+      return fail(ctx, NFCGPU_EINVAL, "tap: in is NULL or not aligned to a sample");
+   if ((inPitch % sampleBytes) || (nBuffers > 1 && inPitch < (uint64_t)n * sampleBytes))
+      return fail(ctx, NFCGPU_EINVAL, "tap: in_pitch_bytes is not a multiple of a sample or smaller than a row");
+   if (!out || ((uintptr_t)out & 3))
+      return fail(ctx, NFCGPU_EINVAL, "tap: out is NULL or not 4-byte aligned");
+   if ((planePitch % 16u) || planePitch < planeBytes)
+      return fail(ctx, NFCGPU_EINVAL, "tap: plane_pitch_bytes is not a multiple of 16 or smaller than a plane");
+   if ((outPitch % 16u) || (nBuffers > 1 && outPitch < (uint64_t)(planes - 1) * planePitch + planeBytes))
+      return fail(ctx, NFCGPU_EINVAL, "tap: out_pitch_bytes is not a multiple of 16 or smaller than the planes of a buffer");
+   if (((uintptr_t)stateIn & 3) || ((uintptr_t)stateOut & 3))
+      return fail(ctx, NFCGPU_EINVAL, "tap: state_in or state_out is not 4-byte aligned");
+   if (params->sample_rate == 0)
+      return fail(ctx, NFCGPU_EINVAL, "tap: sample rate must be non-zero");
+
+   NfcHostParams hp;
+   NfcConfig cfg;
+   hp.sampleRate = params->sample_rate;
+   if (!nfc_build_config(hp, cfg))
+      return fail(ctx, NFCGPU_ERATE, "tap: sample rate not decodable with the fixed history depth");
+
+   if (report)
+      std::memset(report, 0, sizeof(*report));
+
+   HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+   const size_t stateBytes = (size_t)nBuffers * sizeof(NfcTapRecord);
+
+   if (nBuffers == 0)
+      return NFCGPU_OK;
+
+   if (n == 0)
+   {
+      /* nothing walked: state_out is state_in */
+      if (stateOut)
+      {
+         std::vector<nfcgpu_tap_state> fresh;
+
+         if (!stateIn)
+         {
+            fresh.resize(nBuffers);
+            for (nfcgpu_tap_state &s: fresh)
+               nfcgpu_tap_state_init(&s);
+         }
+
+         if (location == NFCGPU_LOC_HOST)
+            std::memmove(stateOut, stateIn ? stateIn : fresh.data(), stateBytes);
+         else
+         {
+            HIP_TRY(ctx, hipMemcpyAsync(stateOut, stateIn ? stateIn : fresh.data(), stateBytes, stateIn ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+         }
+      }
+      return NFCGPU_OK;
+   }
+
+   NfcTapArgs A;
+   std::memset(&A, 0, sizeof(A));
+
+   A.warm = params->chunk_samples ? params->warm_samples : tap_default_warm(params->sample_rate);
+   A.chunk = params->chunk_samples ? params->chunk_samples : tap_default_chunk(nBuffers, n, A.warm);
+   A.chunksPerBuffer = (uint32_t)(((uint64_t)n + A.chunk - 1) / A.chunk);
+   A.n = n;
+   A.nBuffers = nBuffers;
+   A.layout = layout;
+   A.mask = params->channels;
+   A.walkers = (uint64_t)nBuffers * A.chunksPerBuffer;
+
+   if (A.walkers > 0xFFFFFFFFull)
+      return fail(ctx, NFCGPU_EINVAL, "tap: more than 2^32 - 1 chunks (chunk_samples is too small for this much input)");
+
+   const uint32_t C = A.chunksPerBuffer;
+   const uint64_t reach = (uint64_t)(C - 1) * A.chunk; /* where the last chunk of a buffer begins: no warm-up is longer */
+   const uint64_t longest = (A.warm < reach ? A.warm : reach) + (A.chunk < n ? A.chunk : n);
+
+   A.tiles = (uint32_t)((longest + NfcTapShape::kTile - 1) / NfcTapShape::kTile);
+
+   /* scratch: starts, ends, list, frontier, next, count */
+   const size_t statesAt = 0, statesBytes = ((size_t)A.walkers * sizeof(NfcTapState) + 15) & ~(size_t)15;
+   const size_t wordsBytes = ((size_t)nBuffers * 4 + 15) & ~(size_t)15;
+   const size_t listAt = statesAt + 2 * statesBytes, frontierAt = listAt + wordsBytes, nextAt = frontierAt + wordsBytes, countAt = nextAt + wordsBytes;
+   const size_t need = countAt + 16;
+
+   if (need > ctx->tapScratchBytes)
+   {
+      if (ctx->tapScratch)
+         (void)hipFree(ctx->tapScratch);
+      ctx->tapScratch = nullptr;
+      ctx->tapScratchBytes = 0;
+      if (hipMalloc(&ctx->tapScratch, need) != hipSuccess)
+         return fail(ctx, NFCGPU_ENOMEM, "tap: scratch for the walkers' states could not be allocated");
+      ctx->tapScratchBytes = need;
+   }
+
+   if (!ctx->tapCount && hipHostMalloc((void **)&ctx->tapCount, 16, hipHostMallocDefault) != hipSuccess)
+   {
+      ctx->tapCount = nullptr;
+      return fail(ctx, NFCGPU_ENOMEM, "tap: pinned word for the rounds could not be allocated");
+   }
+
+   uint8_t *scratch = (uint8_t *)ctx->tapScratch;
+
+   A.starts = (NfcTapState *)(scratch + statesAt);
+   A.ends = (NfcTapState *)(scratch + statesAt + statesBytes);
+   A.listOut = (uint32_t *)(scratch + listAt);
+   A.frontier = (uint32_t *)(scratch + frontierAt);
+   A.next = (uint32_t *)(scratch + nextAt);
+   A.count = (uint32_t *)(scratch + countAt);
+
+   A.in = (const uint8_t *)in;
+   A.out = out;
+   A.inPitch = inPitch;
+   A.outPitch = outPitch;
+   A.planePitch = planePitch;
+   A.stateIn = (const NfcTapRecord *)stateIn;
+   A.stateOut = (NfcTapRecord *)stateOut;
+
+   /* host memory goes through the staging slots: rows and state_in up through one, planes and state_out back through the other */
+   nfcgpu_ctx::StageSlot *up = nullptr, *down = nullptr;
+
+   struct Release
+   {
+      nfcgpu_ctx *ctx;
+      nfcgpu_ctx::StageSlot **up, **down;
+      ~Release()
+      {
+         if (*up)
+            stage_release(ctx, *up);
+         if (*down)
+            stage_release(ctx, *down);
+      }
+   } release {ctx, &up, &down};
+
+   const size_t rowBytes = (size_t)n * sampleBytes;
+   size_t downPlane = 0, downPitch = 0, downStates = 0;
+
+   ctx->inflight = true;
+
+   if (location == NFCGPU_LOC_HOST)
+   {
+      const size_t upPitch = (rowBytes + 255) & ~(size_t)255, upStates = upPitch * nBuffers;
+
+      int rc = stage_acquire(ctx, upStates + stateBytes, &up);
+      if (rc)
+         return rc;
+
+      for (uint32_t b = 0; b < nBuffers; b++)
+         std::memcpy(up->h + (size_t)b * upPitch, (const uint8_t *)in + (size_t)b * inPitch, rowBytes);
+      if (stateIn)
+         std::memcpy(up->h + upStates, stateIn, stateBytes);
+
+      HIP_TRY(ctx, hipMemcpyAsync(up->d, up->h, upStates + (stateIn ? stateBytes : 0), hipMemcpyHostToDevice, ctx->stream));
+
+      downPlane = ((size_t)planeBytes + 255) & ~(size_t)255;
+      downPitch = downPlane * planes;
+      downStates = downPitch * nBuffers;
+
+      rc = stage_acquire(ctx, downStates + stateBytes, &down);
+      if (rc)
+         return rc;
+
+      A.in = up->d;
+      A.inPitch = upPitch;
+      A.stateIn = stateIn ? (const NfcTapRecord *)(up->d + upStates) : nullptr;
+      A.out = (float *)down->d;
+      A.outPitch = downPitch;
+      A.planePitch = downPlane;
+      A.stateOut = stateOut ? (NfcTapRecord *)(down->d + downStates) : nullptr;
+   }
+
+   const size_t lds = (size_t)(1 + planes) * NfcTapShape::kPlaneFloats * sizeof(float);
+   (void)lds; /* (the emulated test build's launches take no LDS) */
+   auto walk_grid = [](uint64_t walkers) {
+      const uint64_t groups = (walkers + NfcTapShape::kWalkers - 1) / NfcTapShape::kWalkers;
+      return dim3((uint32_t)(groups < (1u << 20) ? groups : (1u << 20)));
+   };
+   const uint64_t seamBlocks = (A.walkers + 255) / 256, listBlocks = ((uint64_t)nBuffers + 255) / 256;
+   const dim3 seamGrid((uint32_t)(seamBlocks < 65536 ? seamBlocks : 65536)), listGrid((uint32_t)(listBlocks < 65536 ? listBlocks : 65536));
+
+   /* the first walk: every chunk */
+   hipLaunchKernelGGL(nfc_tap_walk_kernel, walk_grid(A.walkers), dim3(NfcTapShape::kWalkers), lds, ctx->stream, A, cfg);
+   HIP_TRY(ctx, hipGetLastError());
+
+   uint32_t rounds = 0;
+   uint64_t rewalked = 0;
+
+   if (C > 1)
+   {
+      /* nothing is true yet but the first chunks (a frontier of 0 and of 1 are the same: chunk 0 is never looked at), none found to differ */
+      HIP_TRY(ctx, hipMemsetAsync(A.frontier, 0, wordsBytes, ctx->stream));
+      HIP_TRY(ctx, hipMemsetAsync(A.next, 0xFF, wordsBytes, ctx->stream));
+
+      NfcTapArgs R = A;
+      R.list = A.listOut;
+      R.tiles = ((A.chunk < n ? A.chunk : n) + NfcTapShape::kTile - 1) / NfcTapShape::kTile;
+
+      for (;;)
+      {
+         HIP_TRY(ctx, hipMemsetAsync(A.count, 0, 16, ctx->stream));
+         hipLaunchKernelGGL(nfc_tap_seam_kernel, seamGrid, dim3(256), 0, ctx->stream, A);
+         HIP_TRY(ctx, hipGetLastError());
+         hipLaunchKernelGGL(nfc_tap_list_kernel, listGrid, dim3(256), 0, ctx->stream, A);
+         HIP_TRY(ctx, hipGetLastError());
+         HIP_TRY(ctx, hipMemcpyAsync(ctx->tapCount, A.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+         const uint32_t listed = ctx->tapCount[0];
+
+         if (listed == 0)
+            break;
+
+         /* (every round moves the frontier of every buffer it lists by a chunk at least: C - 1 rounds at the most) */
+         if (rounds >= C - 1 || listed > nBuffers)
+            return fail(ctx, NFCGPU_EHIP, "tap: the rounds of second walks did not end (internal error)");
+
+         rounds++;
+         rewalked += listed;
+         R.walkers = listed;
+         hipLaunchKernelGGL(nfc_tap_walk_kernel, walk_grid(listed), dim3(NfcTapShape::kWalkers), lds, ctx->stream, R, cfg);
+         HIP_TRY(ctx, hipGetLastError());
+      }
+   }
+
+   if (A.stateOut)
+   {
+      hipLaunchKernelGGL(nfc_tap_finish_kernel, listGrid, dim3(256), 0, ctx->stream, A);
+      HIP_TRY(ctx, hipGetLastError());
+   }
+
+   if (location == NFCGPU_LOC_HOST)
+   {
+      HIP_TRY(ctx, hipMemcpyAsync(down->h, down->d, downStates + (stateOut ? stateBytes : 0), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+      /* the planes go to the caller's rows; what lies between them is the caller's */
+      for (uint32_t b = 0; b < nBuffers; b++)
+         for (uint32_t k = 0; k < planes; k++)
+            std::memcpy((uint8_t *)out + (size_t)b * outPitch + (size_t)k * planePitch, down->h + (size_t)b * downPitch + (size_t)k * downPlane, (size_t)planeBytes);
+      if (stateOut)
+         std::memcpy(stateOut, down->h + downStates, stateBytes);
+   }
+   else
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+   if (report)
+   {
+      report->chunks = (uint32_t)A.walkers;
+      report->rounds = rounds;
+      report->rewalked_chunks = (uint32_t)(rewalked > 0xFFFFFFFFull ? 0xFFFFFFFFull : rewalked);
+   }
+
+   return NFCGPU_OK;
+}
+
+int nfcgpu_stream_tap_state(nfcgpu_ctx *ctx, uint32_t id, nfcgpu_tap_state *state)
+{
+   SETTLE_FIRST(ctx);
+
+   if (!ctx || !state)
+      return NFCGPU_EINVAL;
+   if (id >= ctx->maxStreams || !ctx->streams[id].open)
+      return fail(ctx, NFCGPU_ESTREAM, "unknown stream");
+
+   int rc = nfcgpu_sync(ctx);
+   if (rc && rc != NFCGPU_EOVERFLOW)
+      return rc;
+
+   const StreamInfo &si = ctx->streams[id];
+
+   nfcgpu_tap_state_init(state);
+
+   /* a stream never fed starts from nothing; a pending initialize() restarts the clock and carries the front end on (nfc_state_init) */
+   if (si.initialized)
+   {
+      NfcTapState s;
+      HIP_TRY(ctx, hipMemcpy(&s, ctx->dStates + id, sizeof(s), hipMemcpyDeviceToHost));
+      std::memcpy(state, &s, sizeof(s));
+      if (si.needInit)
+         state->clock = 0xFFFFFFFFu;
+   }
+
+   return rc;
 }
 
 int nfcgpu_submit_uniform(nfcgpu_ctx *ctx, uint32_t first, uint32_t count, const void *base, uint64_t pitch, uint32_t n,

@@ -24,6 +24,14 @@ RECORD_SAME, RECORD_MAGNITUDE = 0, 1
 # one nfcgpu_record_levels per buffer
 LEVELS_DTYPE = np.dtype([("power", np.float32), ("average", np.float32), ("peak", np.float32), ("clipped", np.uint32)])
 
+# the planes of nfcgpu_signal_tap (NFCGPU_TAP_*), in the order they are written
+TAP_VALUE, TAP_FILTERED, TAP_DEVIATION, TAP_AVERAGE, TAP_ENVELOPE, TAP_DEPTH = 1, 2, 4, 8, 16, 32
+TAP_ALL = 0x3F
+TAP_NAMES = ("value", "filtered", "deviation", "average", "envelope", "depth")
+# one nfcgpu_tap_state per buffer
+TAP_STATE_DTYPE = np.dtype([("clock", np.uint32), ("pulse_filter", np.uint32), ("envelope", np.float32), ("filter_n1", np.float32),
+                            ("deviation", np.float32), ("average", np.float32), ("reserved", np.uint32, (2,))])
+
 FRAME_CARRIER_OFF, FRAME_CARRIER_ON, FRAME_POLL, FRAME_LISTEN = 0x100, 0x101, 0x102, 0x103
 
 
@@ -116,6 +124,25 @@ class SpectrumParams(ctypes.Structure):
     ]
 
 
+class TapParams(ctypes.Structure):
+    _fields_ = [
+        ("sample_rate", ctypes.c_uint32),
+        ("channels", ctypes.c_uint32),
+        ("chunk_samples", ctypes.c_uint32),
+        ("warm_samples", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 4),
+    ]
+
+
+class TapReport(ctypes.Structure):
+    _fields_ = [
+        ("chunks", ctypes.c_uint32),
+        ("rounds", ctypes.c_uint32),
+        ("rewalked_chunks", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 # the reference's window names (FourierProcessTask.cpp:121-143; see include/nfcgpu.h for what they compute)
 WINDOWS = {"none": 0, "hamming": 1, "hann": 2}
 
@@ -168,6 +195,10 @@ def load_library(path=LIB_PATH):
     lib.nfcgpu_spectrum_frames.restype = u32
     lib.nfcgpu_spectrum.argtypes = [vp, vp, u64, u32, u32, P(SpectrumParams), vp, u64, u32]
     lib.nfcgpu_record.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, u64, vp, u32]
+    lib.nfcgpu_tap_state_init.argtypes = [vp]
+    lib.nfcgpu_tap_state_init.restype = None
+    lib.nfcgpu_signal_tap.argtypes = [vp, vp, u64, u32, u32, u32, u32, P(TapParams), vp, vp, u64, u64, vp, P(TapReport), u32]
+    lib.nfcgpu_stream_tap_state.argtypes = [vp, u32, vp]
     lib.nfcgpu_wav_write.argtypes = [ctypes.c_char_p, vp, u64, u32, u32, u32, vp]
     lib.nfcgpu_wav_append.argtypes = [ctypes.c_char_p, vp, u64]
     lib.nfcgpu_flush.argtypes = [vp, u32]
@@ -392,6 +423,52 @@ class NfcGpu:
         """Same with device pointers (samples, PCM and levels resident in HBM); levels_ptr None skips the levels."""
         self._check(self.lib.nfcgpu_record(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, stride, mode, out_ptr, out_pitch_bytes,
                                            levels_ptr, LOC_DEVICE))
+
+    def tap_state_init(self, count=1):
+        """TAP_STATE_DTYPE [count] of streams just opened (nfcgpu_tap_state_init)."""
+        states = np.zeros(count, dtype=TAP_STATE_DTYPE)
+        for i in range(count):
+            self.lib.nfcgpu_tap_state_init(states.ctypes.data + i * TAP_STATE_DTYPE.itemsize)
+        return states
+
+    def signal_tap(self, buffers, sample_rate, channels=TAP_ALL, stride=1, fmt=FMT_F32, state=None, chunk=0, warm=0):
+        """The front end's per-sample signals of a 2-D array [n_buffers, n * stride] (host memory; float32, or with fmt=FMT_I16
+        int16 PCM) as the decoder forms them (nfcgpu_signal_tap): (dict name -> float32 [n_buffers, n] of the selected
+        channels, TAP_STATE_DTYPE [n_buffers] behind the last sample, TapReport). state: TAP_STATE_DTYPE [n_buffers] to start
+        from, None = streams just opened. chunk, warm: how the buffers are cut (0, 0: the library's choice); results do not
+        depend on it."""
+        buffers = np.ascontiguousarray(buffers, dtype=np.int16 if fmt == FMT_I16 else np.float32)
+        nb, width = buffers.shape
+        assert width % stride == 0
+        n = width // stride
+        names = [name for bit, name in enumerate(TAP_NAMES) if channels >> bit & 1]
+        plane = (n * 4 + 15) & ~15
+        out = np.zeros((nb, max(len(names), 1), plane // 4), dtype=np.float32)
+        if state is not None:
+            state = np.ascontiguousarray(state, dtype=TAP_STATE_DTYPE)
+            assert state.shape == (nb,)
+        states = np.zeros(nb, dtype=TAP_STATE_DTYPE)
+        p = TapParams(sample_rate, channels, chunk, warm)
+        report = TapReport()
+        self._check(self.lib.nfcgpu_signal_tap(self.ctx, buffers.ctypes.data, width * buffers.itemsize, nb, n, stride, fmt, ctypes.byref(p),
+                                               None if state is None else state.ctypes.data, out.ctypes.data, out.shape[1] * plane, plane,
+                                               states.ctypes.data, ctypes.byref(report), LOC_HOST))
+        return {name: np.ascontiguousarray(out[:, k, :n]) for k, name in enumerate(names)}, states, report
+
+    def signal_tap_device(self, in_ptr, in_pitch_bytes, n_buffers, n_samples, sample_rate, out_ptr, out_pitch_bytes, plane_pitch_bytes,
+                          channels=TAP_ALL, stride=1, fmt=FMT_F32, state_in_ptr=None, state_out_ptr=None, chunk=0, warm=0):
+        """Same with device pointers (samples, planes and states resident in HBM); returns the TapReport."""
+        p = TapParams(sample_rate, channels, chunk, warm)
+        report = TapReport()
+        self._check(self.lib.nfcgpu_signal_tap(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, stride, fmt, ctypes.byref(p), state_in_ptr,
+                                               out_ptr, out_pitch_bytes, plane_pitch_bytes, state_out_ptr, ctypes.byref(report), LOC_DEVICE))
+        return report
+
+    def stream_tap_state(self, stream):
+        """TAP_STATE_DTYPE [1]: the front-end state the stream's next buffer will start from (nfcgpu_stream_tap_state)."""
+        state = np.zeros(1, dtype=TAP_STATE_DTYPE)
+        self._check(self.lib.nfcgpu_stream_tap_state(self.ctx, stream, state.ctypes.data))
+        return state
 
     def flush(self, stream):
         self._check(self.lib.nfcgpu_flush(self.ctx, stream))
