@@ -25,6 +25,8 @@
  *                                      load, value = (float)v / 32768.0f: the widening hw::RecordDevice::readScaledSamples<short>
  *                                      does on the host (lib-hw/hw-radio .../RecordDevice.cpp:247-248, 281-311) and the fp32 copy
  *                                      of the capture it makes are skipped
+ *   nfcgpu_spectrum_fmt,               the display consumers of the same buffers - FourierProcessTask (lab-tasks/.../FourierProcessTask.cpp)
+ *   nfcgpu_resample_radio_fmt          and SignalResamplingTask (SignalResamplingTask.cpp:168-226) - reading that format in place too
  *   nfcgpu_flush                       NfcDecoder::nextFrames(invalid buffer) -> one carrier-state frame (NfcDecoder.cpp:449-463)
  *   nfcgpu_poll                        the returned std::list<lab::RawFrame> (lab-data/src/main/cpp/RawFrame.cpp:26-98)
  *   nfcgpu_stream_close                ~NfcDecoder
@@ -229,6 +231,20 @@ int nfcgpu_magnitude_fmt(nfcgpu_ctx *ctx, const void *iq, uint64_t n_samples, fl
  * `out` and `counts` alike. */
 int nfcgpu_resample_radio(nfcgpu_ctx *ctx, const float *in, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_samples,
                           float *out, uint64_t out_pitch_bytes, uint32_t capacity_pairs, uint32_t *counts, uint32_t location);
+/* The same for buffers of samples as the decoder takes them: `stride` 1 magnitude or 2 interleaved IQ, `format` NFCGPU_FMT_*, so
+ * that a capture that is decoded in place is drawn in place. The resampled value is the magnitude the decoder's loader forms of
+ * a sample - (float)v / 32768.0f of int16 (RecordDevice.cpp:247-248, 297-300), and for IQ the formula of nfcgpu_magnitude on the
+ * converted pair (RadioDeviceTask.cpp:626-642), which is what RadioDeviceTask publishes on "radio.signal.raw" for
+ * SignalResamplingTask.cpp:168-226 to read - formed while the kernel loads; the control points of a buffer are bit for bit those
+ * nfcgpu_resample_radio gives for a float buffer holding these magnitudes, and no such buffer is made: host input is staged in
+ * its own format, device input is read in place. `in` and in_pitch_bytes are multiples of a sample (stride * 4 bytes of
+ * NFCGPU_FMT_F32, stride * 2 of NFCGPU_FMT_I16: an int16 magnitude row may start on any 2-byte boundary), in_pitch_bytes at
+ * least n_samples of them; NFCGPU_EINVAL otherwise, as for a stride or format that is not one of these. out, counts,
+ * capacity_pairs, NFCGPU_EOVERFLOW and n_samples >= 25 are as above. With stride 1 and NFCGPU_FMT_F32 it is the call above, to
+ * the error codes and texts (a misaligned `in` is refused here). */
+int nfcgpu_resample_radio_fmt(nfcgpu_ctx *ctx, const void *in, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_samples,
+                              uint32_t stride, uint32_t format, float *out, uint64_t out_pitch_bytes,
+                              uint32_t capacity_pairs, uint32_t *counts, uint32_t location);
 
 /* Spectrum of interleaved float IQ for display: what the reference's FourierProcessTask, the consumer of "radio.signal.iq",
  * publishes on "signal.fft" (lab-tasks/src/main/cpp/tasks/FourierProcessTask.cpp, the SSE2 branches that
@@ -273,6 +289,18 @@ uint32_t nfcgpu_spectrum_frames(const nfcgpu_spectrum_params *p, uint32_t n_pair
  * is complete. Zero frames is success and writes nothing. */
 int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_pairs,
                     const nfcgpu_spectrum_params *params, float *out, uint64_t out_pitch_bytes, uint32_t location);
+/* The same for IQ in `format` (NFCGPU_FMT_*). With NFCGPU_FMT_F32 it is the call above, to the error codes and texts. With
+ * NFCGPU_FMT_I16 a pair is two little-endian int16, I then Q, as a two-channel capture file holds them: iq and in_pitch_bytes are
+ * multiples of 4 (not 8), so a frame, which starts at pair f * hop, starts at any 4-byte boundary. Both components are converted as
+ * they are loaded, (float)v / 32768.0f (RecordDevice.cpp:247-248, 297-300; exact), and then take the window product (:250-262),
+ * the butterflies, the magnitude (:279-341) and the swap of halves (:344-348) of the float call: the floats written are bit for bit
+ * those of nfcgpu_spectrum on a float buffer holding the converted values, and no such buffer is made - host input is staged as
+ * int16, n_pairs * 4 bytes per row, device input is read in place. Frame counts, the n_pairs < L * D guard (:242), `out` and its
+ * pitch, and zero frames being success are those of the float call, and so is what is not checked: in_pitch_bytes may be smaller
+ * than a row in either format (input rows may overlap; they are only read). NFCGPU_EINVAL also for an unknown format. */
+int nfcgpu_spectrum_fmt(nfcgpu_ctx *ctx, const void *iq, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_pairs,
+                        const nfcgpu_spectrum_params *params, float *out, uint64_t out_pitch_bytes, uint32_t location,
+                        uint32_t format);
 
 /* Recording: float samples to the 16-bit PCM of a capture file, with the receiver's levels, in one pass over the input - the
  * per-sample loop of SignalStorageTask::writeRadio (SignalStorageTask.cpp:493-523, hw::RecordDevice::writeScaledSamples<short>,

@@ -7,6 +7,7 @@
  * four points in registers), 256 threads beyond (L / 256 points per thread).
  *
  *   step 0             gather the frame (FourierProcessTask.cpp:250-262: FFT input m is source pair 4 D (m >> 2) + (m & 3)),
+ *                      float pairs or the int16 pairs of a capture file converted as they are loaded (nfc_sample.hpp),
  *                      one fp32 product with the window per component, first radix-4 pass (its twiddles are all 1)
  *   step 2 q - 1       results of pass q - 1 to LDS at their Stockham positions
  *   step 2 q           inputs of pass q from LDS (consecutive lanes read consecutive points), twiddles, butterflies
@@ -31,9 +32,11 @@
 
 #include <stdint.h>
 
+#include "nfc_sample.hpp"
+
 struct NfcSpectrumArgs
 {
-   const float2 *iq;        /* buffer b starts at iq + b * inPitchPairs */
+   const float2 *iq;        /* buffer b starts at iq + b * inPitchPairs; int16 input: NfcIq16 pairs behind this pointer */
    float *out;              /* frame f of buffer b: out + b * outPitchFloats + f * L */
    const float *window;     /* L factors */
    const float2 *twiddle;   /* L entries: exp(-2 pi i n / L), computed in double, rounded to float */
@@ -114,13 +117,27 @@ static __device__ __forceinline__ void nfc_spec_butterfly(float *re, float *im)
    }
 }
 
+/* a source pair as two floats: the pair as it lies (float input), or an int16 pair - one 32-bit load - with both components
+ * converted (nfc_i16_to_float, exact). The kernels exist once per format. */
+static __device__ __forceinline__ float2 nfc_spectrum_pair(float2 v) { return v; }
+static __device__ __forceinline__ float2 nfc_spectrum_pair(NfcIq16 v)
+{
+   float2 pair;
+   pair.x = nfc_i16_to_float(v.i);
+   pair.y = nfc_i16_to_float(v.q);
+   return pair;
+}
+
+template <bool I16> struct NfcSpectrumSource { typedef float2 Pair; };
+template <> struct NfcSpectrumSource<true> { typedef NfcIq16 Pair; };
+
 /* step 0: gather, window, first pass */
-template <int L>
+template <int L, bool I16>
 static __device__ __forceinline__ void nfc_spectrum_load(const NfcSpectrumArgs &A, uint64_t frame, int lane, NfcSpectrumRegs<L> &regs)
 {
    constexpr int T = L / 4, NT = NfcSpectrumShape<L>::kThreads;
    const uint64_t buffer = frame / A.frames, f = frame % A.frames;
-   const float2 *src = A.iq + buffer * A.inPitchPairs + f * A.hop;
+   const typename NfcSpectrumSource<I16>::Pair *src = reinterpret_cast<const typename NfcSpectrumSource<I16>::Pair *>(A.iq) + buffer * A.inPitchPairs + f * A.hop;
    const uint64_t group = 4ull * A.decimation;
 
 #pragma unroll
@@ -133,7 +150,7 @@ static __device__ __forceinline__ void nfc_spectrum_load(const NfcSpectrumArgs &
       for (int r = 0; r < 4; r++)
       {
          const int m = i + r * T;
-         const float2 v = src[group * (uint64_t)(m >> 2) + (uint64_t)(m & 3)];
+         const float2 v = nfc_spectrum_pair(src[group * (uint64_t)(m >> 2) + (uint64_t)(m & 3)]);
          const float w = A.window[m];
          re[r] = nfc_spec_mul(v.x, w);
          im[r] = nfc_spec_mul(v.y, w);
@@ -239,13 +256,14 @@ static __device__ __forceinline__ void nfc_spectrum_store(const NfcSpectrumArgs 
    }
 }
 
-/* step STEP of NfcSpectrumShape<L>::kSteps for thread `lane` of the workgroup that owns `frame`; a barrier belongs between two steps */
-template <int L, int STEP>
+/* step STEP of NfcSpectrumShape<L>::kSteps for thread `lane` of the workgroup that owns `frame`; a barrier belongs between two steps.
+ * I16: the input is int16 pairs; only step 0 knows. */
+template <int L, int STEP, bool I16 = false>
 static __device__ __forceinline__ void nfc_spectrum_step(const NfcSpectrumArgs &A, uint64_t frame, int lane, NfcSpectrumRegs<L> &regs, float *ldsRe,
                                                          float *ldsIm)
 {
    if constexpr (STEP == 0)
-      nfc_spectrum_load<L>(A, frame, lane, regs);
+      nfc_spectrum_load<L, I16>(A, frame, lane, regs);
    else if constexpr (STEP == NfcSpectrumShape<L>::kSteps - 1)
       nfc_spectrum_store<L>(A, frame, lane, regs);
    else if constexpr (STEP & 1)

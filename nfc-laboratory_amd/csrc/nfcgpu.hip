@@ -29,6 +29,7 @@
 #include "nfc_spectrum.hpp"
 #include "nfc_sample.hpp"
 #include "nfc_record.hpp"
+#include "nfc_resample.hpp"
 #ifdef NFCGPU_EMULATED_TEST_BUILD
 /* (the twins of the tap kernels walk the decoder's step machine: nfc_core.hpp as the CPU builds of tests/hostsim compile it) */
 #define NFC_DEV static inline
@@ -90,17 +91,17 @@ __global__ void nfc_wave_kernel_i16(const NfcConfig *__restrict__ cfgPtr, NfcLau
  * steps and the threads of a workgroup as loops, the end of a loop over the threads where the device has a barrier. */
 namespace {
 
-template <int L, int STEP>
+template <int L, int STEP, bool I16>
 void spectrum_twin_steps(const NfcSpectrumArgs &A, uint64_t frame, NfcSpectrumRegs<L> *regs, float *ldsRe, float *ldsIm)
 {
    for (int lane = 0; lane < NfcSpectrumShape<L>::kThreads; lane++)
-      nfc_spectrum_step<L, STEP>(A, frame, lane, regs[lane], ldsRe, ldsIm);
+      nfc_spectrum_step<L, STEP, I16>(A, frame, lane, regs[lane], ldsRe, ldsIm);
 
    if constexpr (STEP + 1 < NfcSpectrumShape<L>::kSteps)
-      spectrum_twin_steps<L, STEP + 1>(A, frame, regs, ldsRe, ldsIm);
+      spectrum_twin_steps<L, STEP + 1, I16>(A, frame, regs, ldsRe, ldsIm);
 }
 
-template <int L>
+template <int L, bool I16>
 void spectrum_twin(const NfcSpectrumArgs &A)
 {
    static NfcSpectrumRegs<L> regs[NfcSpectrumShape<L>::kThreads];
@@ -108,14 +109,17 @@ void spectrum_twin(const NfcSpectrumArgs &A)
 
    for (uint64_t block = 0; block < fakehip::launchGrid.x; block++)
       for (uint64_t frame = block; frame < A.total; frame += fakehip::launchGrid.x)
-         spectrum_twin_steps<L, 0>(A, frame, regs, ldsRe, ldsIm);
+         spectrum_twin_steps<L, 0, I16>(A, frame, regs, ldsRe, ldsIm);
 }
 
 }
 #define NFC_SPECTRUM_KERNEL(L) \
-   void nfc_spectrum_kernel_##L(NfcSpectrumArgs A) { spectrum_twin<L>(A); }
+   void nfc_spectrum_kernel_##L(NfcSpectrumArgs A) { spectrum_twin<L, false>(A); } \
+   void nfc_spectrum_kernel_i16_##L(NfcSpectrumArgs A) { spectrum_twin<L, true>(A); }
 #else
-#define NFC_SPECTRUM_KERNEL(L) __global__ void nfc_spectrum_kernel_##L(NfcSpectrumArgs A);
+#define NFC_SPECTRUM_KERNEL(L) \
+   __global__ void nfc_spectrum_kernel_##L(NfcSpectrumArgs A); \
+   __global__ void nfc_spectrum_kernel_i16_##L(NfcSpectrumArgs A);
 #endif
 NFC_SPECTRUM_KERNEL(256)
 NFC_SPECTRUM_KERNEL(512)
@@ -123,6 +127,47 @@ NFC_SPECTRUM_KERNEL(1024)
 NFC_SPECTRUM_KERNEL(2048)
 NFC_SPECTRUM_KERNEL(4096)
 #undef NFC_SPECTRUM_KERNEL
+
+#ifdef NFCGPU_EMULATED_TEST_BUILD
+/* The test build's twins of the resampler kernels of nfc_resample.hip: buffer after buffer, the tiles and the ring of
+ * nfc_resample.hpp, a sample converted on its way into the ring and decided from there by the text the device compiles. (The float
+ * magnitude kernel's twin is tests/hostsim/emu_kernels.cpp's, as it was.) */
+namespace {
+
+template <uint32_t LAYOUT>
+void resample_twin(const NfcResampleArgs &A)
+{
+   using S = NfcResampleShape;
+
+   float ring[S::kPitch];
+
+   for (uint32_t buffer = 0; buffer < A.nBuffers; buffer++)
+   {
+      NfcResampleLane s;
+      nfc_resample_begin(s);
+
+      for (uint32_t base = 0; base < A.n; base += S::kTile)
+      {
+         for (uint32_t col = 0; col < S::kTile; col++)
+            ring[(base % S::kRing) + col] = nfc_resample_sample<LAYOUT>(A, buffer, base + col);
+
+         nfc_resample_decide(A, buffer, true, s, ring, base);
+      }
+
+      nfc_resample_end(A, buffer, true, s);
+   }
+}
+
+}
+#define NFC_RESAMPLE_KERNEL(name, LAYOUT) \
+   void name(NfcResampleArgs A) { resample_twin<LAYOUT>(A); }
+#else
+#define NFC_RESAMPLE_KERNEL(name, LAYOUT) __global__ void name(NfcResampleArgs A);
+#endif
+NFC_RESAMPLE_KERNEL(nfc_resample_radio_kernel_i16, NFC_SAMPLE_I16 | 1u)
+NFC_RESAMPLE_KERNEL(nfc_resample_radio_kernel_iq_i16, NFC_SAMPLE_I16 | 2u)
+NFC_RESAMPLE_KERNEL(nfc_resample_radio_kernel_iq, 2u)
+#undef NFC_RESAMPLE_KERNEL
 
 #ifdef NFCGPU_EMULATED_TEST_BUILD
 /* The test build's twins of the record kernels (nfc_record.hip): the quads, lanes, waves and segments of nfc_record.hpp as loops,
@@ -4278,6 +4323,110 @@ int nfcgpu_resample_radio(nfcgpu_ctx *ctx, const float *in, uint64_t inPitch, ui
    return NFCGPU_OK;
 }
 
+/* The same for rows of any sample layout (nfc_sample.hpp). Float magnitude rows are the call above; the others take the kernels of
+ * nfc_resample.hip, which form the loader's magnitude of a sample while they stage it. Host rows are staged as they are. */
+int nfcgpu_resample_radio_fmt(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, uint32_t stride, uint32_t format,
+                              float *out, uint64_t outPitch, uint32_t capacityPairs, uint32_t *counts, uint32_t location)
+{
+   SETTLE_FIRST(ctx);
+
+   if (!ctx)
+      return NFCGPU_EINVAL;
+   if ((stride != 1 && stride != 2) || (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16))
+      return fail(ctx, NFCGPU_EINVAL, "resampler: stride is not 1 or 2, or the format is unknown");
+
+   const uint32_t layout = stride | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u);
+   const uint32_t sampleBytes = nfc_sample_bytes(layout);
+
+   /* (float magnitude rows: everything but the alignment of `in`, which that call leaves to its caller, is refused there as it is) */
+   if (((uintptr_t)in % sampleBytes) != 0 || (layout != 1u && (inPitch % sampleBytes) != 0))
+      return fail(ctx, NFCGPU_EINVAL, "resampler: in or in_pitch_bytes is not a multiple of a sample");
+
+   if (layout == 1u)
+      return nfcgpu_resample_radio(ctx, (const float *)in, inPitch, nBuffers, n, out, outPitch, capacityPairs, counts, location);
+
+   if (!in || !out || !counts || n < 25 || (outPitch & 7) || ((uintptr_t)out & 7) || inPitch < (uint64_t)n * sampleBytes ||
+       outPitch < (uint64_t)capacityPairs * 8 || (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE))
+      return NFCGPU_EINVAL;
+   if (nBuffers == 0)
+      return NFCGPU_OK;
+
+   HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+   NfcResampleArgs A;
+   std::memset(&A, 0, sizeof(A));
+   A.in = (const uint8_t *)in;
+   A.out = out;
+   A.counts = counts;
+   A.inPitchBytes = inPitch;
+   A.outPitchFloats = outPitch / 4;
+   A.nBuffers = nBuffers;
+   A.n = n;
+   A.capacityPairs = capacityPairs;
+   A.layout = layout;
+
+   uint8_t *scratch = nullptr;
+   std::vector<uint32_t> hostCounts(nBuffers);
+
+   /* what the rows span: the pitch between them, the samples of the last one; out and counts behind it, 8-byte aligned */
+   const size_t inBytes = (size_t)inPitch * (nBuffers - 1) + (size_t)n * sampleBytes, inSpace = (inBytes + 7) & ~(size_t)7;
+   const size_t outBytes = (size_t)outPitch * nBuffers, cntBytes = (size_t)nBuffers * 4;
+
+   if (location == NFCGPU_LOC_HOST)
+   {
+      /* one temporary device block: input in its own format, output, counts (this entry point is not on the streaming path) */
+      if (hipMalloc((void **)&scratch, inSpace + outBytes + cntBytes) != hipSuccess)
+         return fail(ctx, NFCGPU_ENOMEM, "resampler scratch allocation failed");
+
+      hipError_t err = hipMemcpy(scratch, in, inBytes, hipMemcpyHostToDevice);
+      if (err != hipSuccess)
+      {
+         (void)hipFree(scratch);
+         return fail(ctx, NFCGPU_EHIP, "hipMemcpy(H2D resampler input)", err);
+      }
+
+      A.in = scratch;
+      A.out = (float *)(scratch + inSpace);
+      A.counts = (uint32_t *)(scratch + inSpace + outBytes);
+   }
+
+   const dim3 grid((nBuffers + NfcResampleShape::kLanes - 1) / NfcResampleShape::kLanes), block(NfcResampleShape::kLanes);
+
+   switch (layout)
+   {
+      case NFC_SAMPLE_I16 | 1u: hipLaunchKernelGGL(nfc_resample_radio_kernel_i16, grid, block, 0, ctx->stream, A); break;
+      case NFC_SAMPLE_I16 | 2u: hipLaunchKernelGGL(nfc_resample_radio_kernel_iq_i16, grid, block, 0, ctx->stream, A); break;
+      default: hipLaunchKernelGGL(nfc_resample_radio_kernel_iq, grid, block, 0, ctx->stream, A); break;
+   }
+
+   hipError_t err = hipGetLastError();
+   if (err == hipSuccess)
+      err = hipStreamSynchronize(ctx->stream);
+
+   if (err == hipSuccess)
+      err = hipMemcpy(hostCounts.data(), A.counts, cntBytes, hipMemcpyDeviceToHost);
+
+   if (err == hipSuccess && location == NFCGPU_LOC_HOST)
+   {
+      err = hipMemcpy(out, A.out, outBytes, hipMemcpyDeviceToHost);
+      std::memcpy(counts, hostCounts.data(), cntBytes);
+   }
+
+   if (scratch)
+      (void)hipFree(scratch);
+
+   if (err != hipSuccess)
+      return fail(ctx, NFCGPU_EHIP, "adaptive resampler", err);
+
+   for (uint32_t b = 0; b < nBuffers; b++)
+   {
+      if (hostCounts[b] > capacityPairs)
+         return fail(ctx, NFCGPU_EOVERFLOW, "resampler output capacity exceeded: raise capacity_pairs");
+   }
+
+   return NFCGPU_OK;
+}
+
 /* ---- nfcgpu_spectrum: FourierProcessTask::process() (FourierProcessTask.cpp:236-355) for every frame of every buffer ---- */
 
 /* what is wrong with the parameters, or nullptr; *decimation = the D in force */
@@ -4384,22 +4533,35 @@ uint32_t nfcgpu_spectrum_frames(const nfcgpu_spectrum_params *p, uint32_t nPairs
 int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t nBuffers, uint32_t nPairs, const nfcgpu_spectrum_params *params,
                     float *out, uint64_t outPitch, uint32_t location)
 {
+   return nfcgpu_spectrum_fmt(ctx, iq, inPitch, nBuffers, nPairs, params, out, outPitch, location, NFCGPU_FMT_F32);
+}
+
+/* (a pair is 8 bytes of float input and 4 of int16; nothing else differs on the host: the rows are staged as they are and the
+ * kernel of the format converts while it gathers) */
+int nfcgpu_spectrum_fmt(nfcgpu_ctx *ctx, const void *iq, uint64_t inPitch, uint32_t nBuffers, uint32_t nPairs, const nfcgpu_spectrum_params *params,
+                        float *out, uint64_t outPitch, uint32_t location, uint32_t format)
+{
    SETTLE_FIRST(ctx);
 
    if (!ctx)
       return NFCGPU_EINVAL;
+   if (format != NFCGPU_FMT_F32 && format != NFCGPU_FMT_I16)
+      return fail(ctx, NFCGPU_EINVAL, "spectrum: unknown format");
+
+   const bool i16 = format == NFCGPU_FMT_I16;
+   const uint32_t pairBytes = i16 ? 4 : 8;
 
    uint32_t decimation = 1;
    if (const char *why = spectrum_check(params, &decimation))
       return fail(ctx, NFCGPU_EINVAL, why);
-   if (!iq || ((uintptr_t)iq & 7))
-      return fail(ctx, NFCGPU_EINVAL, "spectrum: iq is NULL or not 8-byte aligned");
+   if (!iq || ((uintptr_t)iq & (pairBytes - 1)))
+      return fail(ctx, NFCGPU_EINVAL, i16 ? "spectrum: iq is NULL or not 4-byte aligned" : "spectrum: iq is NULL or not 8-byte aligned");
    if (!out || ((uintptr_t)out & 3))
       return fail(ctx, NFCGPU_EINVAL, "spectrum: out is NULL or not 4-byte aligned");
    if (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE)
       return fail(ctx, NFCGPU_EINVAL, "spectrum: unknown location");
-   if (inPitch & 7)
-      return fail(ctx, NFCGPU_EINVAL, "spectrum: in_pitch_bytes is not a multiple of 8");
+   if (inPitch & (pairBytes - 1))
+      return fail(ctx, NFCGPU_EINVAL, i16 ? "spectrum: in_pitch_bytes is not a multiple of 4" : "spectrum: in_pitch_bytes is not a multiple of 8");
 
    const uint32_t L = params->length;
    const uint32_t frames = spectrum_frames(params, decimation, nPairs);
@@ -4421,7 +4583,7 @@ int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t
 
    uint8_t *scratch = nullptr;
    /* what the buffers span: the pitch between them, the data of the last one */
-   const size_t inBytes = (size_t)inPitch * (nBuffers - 1) + (size_t)nPairs * 8, outBytes = (size_t)outPitch * (nBuffers - 1) + (size_t)rowBytes;
+   const size_t inBytes = (size_t)inPitch * (nBuffers - 1) + (size_t)nPairs * pairBytes, outBytes = (size_t)outPitch * (nBuffers - 1) + (size_t)rowBytes;
 
    A.iq = (const float2 *)iq;
    A.out = out;
@@ -4443,7 +4605,7 @@ int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t
       A.out = (float *)(scratch + inBytes);
    }
 
-   A.inPitchPairs = inPitch / 8;
+   A.inPitchPairs = inPitch / pairBytes;
    A.outPitchFloats = outPitch / 4;
    A.total = (uint64_t)nBuffers * frames;
    A.frames = frames;
@@ -4453,14 +4615,18 @@ int nfcgpu_spectrum(nfcgpu_ctx *ctx, const float *iq, uint64_t inPitch, uint32_t
    /* one workgroup per frame; beyond 2^20 workgroups each takes several frames */
    const dim3 grid((uint32_t)(A.total < (1u << 20) ? A.total : (1u << 20)));
 
+#define NFC_SPECTRUM_LAUNCH(L) \
+   hipLaunchKernelGGL(i16 ? nfc_spectrum_kernel_i16_##L : nfc_spectrum_kernel_##L, grid, dim3(NfcSpectrumShape<L>::kThreads), 0, ctx->stream, A)
+
    switch (L)
    {
-      case 256: hipLaunchKernelGGL(nfc_spectrum_kernel_256, grid, dim3(NfcSpectrumShape<256>::kThreads), 0, ctx->stream, A); break;
-      case 512: hipLaunchKernelGGL(nfc_spectrum_kernel_512, grid, dim3(NfcSpectrumShape<512>::kThreads), 0, ctx->stream, A); break;
-      case 1024: hipLaunchKernelGGL(nfc_spectrum_kernel_1024, grid, dim3(NfcSpectrumShape<1024>::kThreads), 0, ctx->stream, A); break;
-      case 2048: hipLaunchKernelGGL(nfc_spectrum_kernel_2048, grid, dim3(NfcSpectrumShape<2048>::kThreads), 0, ctx->stream, A); break;
-      default: hipLaunchKernelGGL(nfc_spectrum_kernel_4096, grid, dim3(NfcSpectrumShape<4096>::kThreads), 0, ctx->stream, A); break;
+      case 256: NFC_SPECTRUM_LAUNCH(256); break;
+      case 512: NFC_SPECTRUM_LAUNCH(512); break;
+      case 1024: NFC_SPECTRUM_LAUNCH(1024); break;
+      case 2048: NFC_SPECTRUM_LAUNCH(2048); break;
+      default: NFC_SPECTRUM_LAUNCH(4096); break;
    }
+#undef NFC_SPECTRUM_LAUNCH
 
    hipError_t err = hipGetLastError();
    if (err == hipSuccess)

@@ -189,11 +189,13 @@ def load_library(path=LIB_PATH):
     lib.nfcgpu_submit_uniform_fmt.argtypes = [vp, u32, u32, vp, u64, u32, u32, u32, u32, u32]
     lib.nfcgpu_magnitude_fmt.argtypes = [vp, vp, u64, vp, u32, u32]
     lib.nfcgpu_resample_radio.argtypes = [vp, vp, u64, u32, u32, vp, u64, u32, vp, u32]
+    lib.nfcgpu_resample_radio_fmt.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, u64, u32, vp, u32]
     lib.nfcgpu_spectrum_default_params.argtypes = [P(SpectrumParams)]
     lib.nfcgpu_spectrum_default_params.restype = None
     lib.nfcgpu_spectrum_frames.argtypes = [P(SpectrumParams), u32]
     lib.nfcgpu_spectrum_frames.restype = u32
     lib.nfcgpu_spectrum.argtypes = [vp, vp, u64, u32, u32, P(SpectrumParams), vp, u64, u32]
+    lib.nfcgpu_spectrum_fmt.argtypes = [vp, vp, u64, u32, u32, P(SpectrumParams), vp, u64, u32, u32]
     lib.nfcgpu_record.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, u64, vp, u32]
     lib.nfcgpu_tap_state_init.argtypes = [vp]
     lib.nfcgpu_tap_state_init.restype = None
@@ -355,22 +357,35 @@ class NfcGpu:
         self._check(self.lib.nfcgpu_magnitude_fmt(self.ctx, iq.ctypes.data, n, out.ctypes.data, LOC_HOST, fmt))
         return out
 
-    def resample_radio(self, buffers, capacity_pairs=None):
-        """Adaptive (value, offset) control points of each row of a 2-D float32 array of magnitude buffers (host memory);
-        returns a list of (pairs, 2) arrays."""
-        buffers = np.ascontiguousarray(buffers, dtype=np.float32)
-        nb, n = buffers.shape
+    def resample_radio(self, buffers, capacity_pairs=None, stride=1, fmt=FMT_F32):
+        """Adaptive (value, offset) control points of each row of a 2-D array [n_buffers, n * stride] of buffers (host memory):
+        float32 magnitudes, or with stride=2 interleaved IQ, or with fmt=FMT_I16 the int16 PCM of a capture file - the format is
+        what `fmt` says, never the array's dtype. The resampled value is the magnitude the decoder forms of a sample. Returns a
+        list of (pairs, 2) arrays."""
+        buffers = np.ascontiguousarray(buffers, dtype=np.int16 if fmt == FMT_I16 else np.float32)
+        nb, width = buffers.shape
+        assert stride and width % stride == 0
+        n = width // stride
         cap = capacity_pairs or (n + n // 255 + 2)
         out = np.zeros((nb, 2 * cap), dtype=np.float32)
         counts = np.zeros(nb, dtype=np.uint32)
-        self._check(self.lib.nfcgpu_resample_radio(self.ctx, buffers.ctypes.data, n * 4, nb, n, out.ctypes.data, 2 * cap * 4, cap,
-                                                   counts.ctypes.data, LOC_HOST))
+        if stride == 1 and fmt == FMT_F32:
+            self._check(self.lib.nfcgpu_resample_radio(self.ctx, buffers.ctypes.data, n * 4, nb, n, out.ctypes.data, 2 * cap * 4, cap,
+                                                       counts.ctypes.data, LOC_HOST))
+        else:
+            self._check(self.lib.nfcgpu_resample_radio_fmt(self.ctx, buffers.ctypes.data, width * buffers.itemsize, nb, n, stride, fmt,
+                                                           out.ctypes.data, 2 * cap * 4, cap, counts.ctypes.data, LOC_HOST))
         return [out[b, :2 * counts[b]].reshape(-1, 2) for b in range(nb)]
 
-    def resample_radio_device(self, in_ptr, in_pitch_bytes, n_buffers, n_samples, out_ptr, out_pitch_bytes, capacity_pairs, counts_ptr):
+    def resample_radio_device(self, in_ptr, in_pitch_bytes, n_buffers, n_samples, out_ptr, out_pitch_bytes, capacity_pairs, counts_ptr,
+                              stride=1, fmt=FMT_F32):
         """Same with device pointers (input, output and counts resident in HBM)."""
-        self._check(self.lib.nfcgpu_resample_radio(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, out_ptr, out_pitch_bytes,
-                                                   capacity_pairs, counts_ptr, LOC_DEVICE))
+        if stride == 1 and fmt == FMT_F32:
+            self._check(self.lib.nfcgpu_resample_radio(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, out_ptr, out_pitch_bytes,
+                                                       capacity_pairs, counts_ptr, LOC_DEVICE))
+        else:
+            self._check(self.lib.nfcgpu_resample_radio_fmt(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, stride, fmt, out_ptr,
+                                                           out_pitch_bytes, capacity_pairs, counts_ptr, LOC_DEVICE))
 
     def spectrum_params(self, length=1024, window="hamming", decimation=0, hop=0, sample_rate=10000000):
         p = SpectrumParams()
@@ -383,26 +398,36 @@ class NfcGpu:
         """Frames a buffer of n_pairs IQ pairs gives with these parameters (nfcgpu_spectrum_frames)."""
         return self.lib.nfcgpu_spectrum_frames(ctypes.byref(self.spectrum_params(**params)), n_pairs)
 
-    def spectrum(self, buffers, length=1024, window="hamming", decimation=0, hop=0, sample_rate=10000000):
-        """Magnitude spectra of a float32 array [n_buffers, n_pairs, 2] of IQ buffers (host memory), as the reference's
-        FourierProcessTask publishes them (negative frequencies first): [n_buffers, frames, length]; hop = 0 gives the one
-        frame the task publishes for a buffer, hop > 0 a frame every hop pairs."""
-        buffers = np.ascontiguousarray(buffers, dtype=np.float32)
+    def spectrum(self, buffers, length=1024, window="hamming", decimation=0, hop=0, sample_rate=10000000, fmt=FMT_F32):
+        """Magnitude spectra of an array [n_buffers, n_pairs, 2] of IQ buffers (host memory) - float32, or with fmt=FMT_I16 the
+        int16 PCM of a two-channel capture file, converted v / 32768 as it is loaded; the format is what `fmt` says, never the
+        array's dtype - as the reference's FourierProcessTask publishes them (negative frequencies first):
+        [n_buffers, frames, length]; hop = 0 gives the one frame the task publishes for a buffer, hop > 0 a frame every hop
+        pairs."""
+        buffers = np.ascontiguousarray(buffers, dtype=np.int16 if fmt == FMT_I16 else np.float32)
         nb, n, two = buffers.shape
         assert two == 2
         p = self.spectrum_params(length, window, decimation, hop, sample_rate)
         frames = self.lib.nfcgpu_spectrum_frames(ctypes.byref(p), n)
         out = np.zeros((nb, frames, length), dtype=np.float32)
-        self._check(self.lib.nfcgpu_spectrum(self.ctx, buffers.ctypes.data, n * 8, nb, n, ctypes.byref(p), out.ctypes.data,
-                                             frames * length * 4, LOC_HOST))
+        if fmt == FMT_F32:
+            self._check(self.lib.nfcgpu_spectrum(self.ctx, buffers.ctypes.data, n * 8, nb, n, ctypes.byref(p), out.ctypes.data,
+                                                 frames * length * 4, LOC_HOST))
+        else:
+            self._check(self.lib.nfcgpu_spectrum_fmt(self.ctx, buffers.ctypes.data, n * 2 * buffers.itemsize, nb, n, ctypes.byref(p),
+                                                     out.ctypes.data, frames * length * 4, LOC_HOST, fmt))
         return out
 
     def spectrum_device(self, in_ptr, in_pitch_bytes, n_buffers, n_pairs, out_ptr, out_pitch_bytes, length=1024, window="hamming",
-                        decimation=0, hop=0, sample_rate=10000000):
+                        decimation=0, hop=0, sample_rate=10000000, fmt=FMT_F32):
         """Same with device pointers (IQ and spectra resident in HBM); returns the frames written per buffer."""
         p = self.spectrum_params(length, window, decimation, hop, sample_rate)
-        self._check(self.lib.nfcgpu_spectrum(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_pairs, ctypes.byref(p), out_ptr,
-                                             out_pitch_bytes, LOC_DEVICE))
+        if fmt == FMT_F32:
+            self._check(self.lib.nfcgpu_spectrum(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_pairs, ctypes.byref(p), out_ptr,
+                                                 out_pitch_bytes, LOC_DEVICE))
+        else:
+            self._check(self.lib.nfcgpu_spectrum_fmt(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_pairs, ctypes.byref(p), out_ptr,
+                                                     out_pitch_bytes, LOC_DEVICE, fmt))
         return self.lib.nfcgpu_spectrum_frames(ctypes.byref(p), n_pairs)
 
     def record(self, buffers, stride=1, mode=RECORD_SAME, levels=True):
