@@ -410,6 +410,65 @@ int nfcgpu_signal_tap(nfcgpu_ctx *ctx, const void *in, uint64_t in_pitch_bytes, 
 
 int nfcgpu_stream_tap_state(nfcgpu_ctx *ctx, uint32_t stream_id, nfcgpu_tap_state *state /* host */);
 
+/* The tap reduced over sample ranges: for every range and every channel selected in tap->channels min, max, where they lie, the
+ * mean and the count of the values nfcgpu_signal_tap would have written for those samples - a few numbers per frame (the depth
+ * a frame reached, at what envelope) or per pixel column of an overview of a long capture - without a plane ever reaching the
+ * caller. in, in_pitch_bytes, n_buffers, n_samples, stride, format, tap, state_in, state_out and report are those of
+ * nfcgpu_signal_tap and are refused for the same reasons with the same codes; report is the sum over the slabs (below).
+ * `location` applies to in, state_in, state_out, ranges and out; `out` is 4-byte aligned.
+ *
+ * Ranges. Range r is the samples first ... first + count - 1 of buffer `buffer`; ranges may overlap and come in any order. With
+ * ranges == NULL (n_ranges must be 0, reduce->bin_samples > 0) every buffer is cut into bins = ceil(n_samples / bin_samples) bins
+ * of bin_samples samples (the last one may be short) and range r is bin r % bins of buffer r / bins. With K channels selected the
+ * record of range r and the k-th selected channel (bit order) is out[r * K + k].
+ *
+ * A record. Let p be the plane nfcgpu_signal_tap writes for the buffer and channel, and S the samples of the range where p is no
+ * NaN (the depth of a first sample of 0 is one). valid = |S|. argmin is the smallest index i in S (a sample index of the buffer)
+ * such that no j in S has p[j] < p[i], and min is p[argmin] with its bits: a -0.0 stays -0.0, infinities are ordinary values;
+ * max and argmax likewise with >. mean is the sum of p over S, taken in double, divided by valid and rounded once to float. An
+ * empty S (count == 0, or nothing but NaNs) gives min = max = mean = the quiet NaN 0x7FC00000, argmin = argmax = 0xFFFFFFFF,
+ * valid = 0. reserved is written as zero. min, max, argmin, argmax and valid do not depend on how the tap or the reduction cut
+ * the buffers, on scratch_bytes, the other ranges, the other buffers or the run. mean is the same bits from run to run and for
+ * any scratch_bytes: the order of its additions depends only on a sample's offset within its range (segments of 16 384 samples,
+ * within one the quads of four a lane of a wave takes, a butterfly over the wave, the segments in order); it is within
+ * 2^-24 |m| + (ceil(count / 64) + 7) 2^-53 mean(|p|) of the exact mean m.
+ *
+ * Memory. The planes exist only in scratch the context owns (freed by nfcgpu_shutdown): the tap runs over a slab of whole buffers,
+ * as many as fit into scratch_bytes of planes (4 * n_samples rounded up to 256, times K, per buffer) and at least one, the slab is
+ * reduced, the next follows. Every slab pays the tap's rounds of second walks anew, so scratch_bytes == 0 takes all the planes at
+ * once where they fit into three quarters of the device memory that is free, and as many buffers as do otherwise. Host input is
+ * uploaded once. Beside the planes the call holds 32 bytes
+ * per segment of 16 384 samples (or part of one) of every range of a slab and channel, and 8 per segment of every range given.
+ *
+ * NFCGPU_EINVAL, beyond the tap's: reduce NULL or with non-zero reserved fields; ranges == NULL with bin_samples == 0 or
+ * n_ranges != 0; out NULL or misaligned; more than 2^32 - 1 records; a range with buffer >= n_buffers, first + count > n_samples
+ * or reserved != 0. Ranges in host memory are checked before anything runs: the call writes nothing. Ranges in device memory are
+ * checked by the kernels, which read nothing through such a range: it gets the empty record, every other record and state_out
+ * are complete, and the call returns NFCGPU_EINVAL. n_ranges == 0 with ranges != NULL and n_samples == 0 (every range then has
+ * count 0) are success, state_out as the tap leaves it; n_buffers == 0 is success and writes nothing. */
+typedef struct nfcgpu_tap_range { uint32_t buffer, first, count, reserved; } nfcgpu_tap_range;
+
+typedef struct nfcgpu_tap_stat {   /* 32 bytes: one channel over one range */
+   float min, max, mean;
+   uint32_t valid;                 /* samples of the range whose value is not a NaN */
+   uint32_t argmin, argmax;        /* sample index in the buffer */
+   uint32_t reserved[2];           /* written as zero */
+} nfcgpu_tap_stat;
+
+typedef struct nfcgpu_tap_reduce_params {
+   uint32_t bin_samples;    /* with ranges == NULL: samples of a bin */
+   uint32_t reserved0;      /* zero */
+   uint64_t scratch_bytes;  /* bound on the device memory the call uses for planes at a time; 0 = what three quarters of the free device memory hold. At least one buffer is always taken */
+   uint32_t reserved[4];    /* zero */
+} nfcgpu_tap_reduce_params;
+
+int nfcgpu_signal_tap_reduce(nfcgpu_ctx *ctx, const void *in, uint64_t in_pitch_bytes, uint32_t n_buffers, uint32_t n_samples,
+                             uint32_t stride, uint32_t format, const nfcgpu_tap_params *tap, const nfcgpu_tap_reduce_params *reduce,
+                             const nfcgpu_tap_state *state_in /* n_buffers, NULL = all freshly opened */,
+                             const nfcgpu_tap_range *ranges /* n_ranges, NULL = bins */, uint32_t n_ranges,
+                             nfcgpu_tap_stat *out /* records */, nfcgpu_tap_state *state_out /* n_buffers, may be NULL */,
+                             nfcgpu_tap_report *report /* host memory, may be NULL */, uint32_t location);
+
 /* Capture files as hw::RecordDevice writes them (RecordDevice.cpp:493-546, structures :53-100), host only, no context and
  * no device: a 92-byte header - RIFF / WAVE; "fmt " (16: PCM 1, channels, rate, byte rate, block align, 16 bits); "META" (40:
  * "meta", epoch = stream_time, keys[8], the first `channels` taken from `keys`, NULL = zeros); "data" - then the samples,

@@ -39,6 +39,7 @@ static inline uint32_t tap_twin_add(uint32_t *p, uint32_t v) { const uint32_t ol
 #include "nfc_core.hpp"
 #endif
 #include "nfc_tap.hpp"
+#include "nfc_tap_reduce.hpp"
 
 __global__ void nfc_demod_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
 __global__ void nfc_demod_exact_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
@@ -355,7 +356,31 @@ void nfc_tap_finish_kernel(NfcTapArgs A)
    for (uint32_t b = 0; b < A.nBuffers; b++)
       nfc_tap_finish(A, b);
 }
+
+/* ... and of the kernels that reduce its planes (nfc_tap_reduce.hip): the units, the lanes and the butterfly of nfc_tap_reduce.hpp
+ * as loops, every sum in the order the device takes it. */
+void nfc_tap_reduce_kernel(NfcTapReduceArgs A)
+{
+   for (uint64_t j = 0; j < A.units; j++)
+   {
+      NfcTapPartial lanes[64];
+
+      for (uint32_t lane = 0; lane < 64; lane++)
+         lanes[lane] = nfc_tap_reduce_lane(A, j, lane);
+
+      record_twin_butterfly(lanes, [](const NfcTapPartial &x, const NfcTapPartial &y) { return nfc_tap_partial_merge(x, y); });
+      A.partials[j] = lanes[0];
+   }
+}
+
+void nfc_tap_reduce_finish_kernel(NfcTapReduceArgs A)
+{
+   for (uint64_t t = 0; t < A.items * A.channels; t++)
+      nfc_tap_reduce_finish(A, t);
+}
 #else
+__global__ void nfc_tap_reduce_kernel(NfcTapReduceArgs A);
+__global__ void nfc_tap_reduce_finish_kernel(NfcTapReduceArgs A);
 __global__ void nfc_tap_walk_kernel(NfcTapArgs A, NfcConfig cfg);
 __global__ void nfc_tap_seam_kernel(NfcTapArgs A);
 __global__ void nfc_tap_list_kernel(NfcTapArgs A);
@@ -751,6 +776,9 @@ struct nfcgpu_ctx
    void *tapScratch = nullptr;
    size_t tapScratchBytes = 0;
    uint32_t *tapCount = nullptr;
+   /* nfcgpu_signal_tap_reduce: the planes of a slab, the partials of its units and the flag word (device), grown on demand, kept */
+   void *tapReduceScratch = nullptr;
+   size_t tapReduceScratchBytes = 0;
 };
 
 namespace {
@@ -3728,6 +3756,8 @@ int nfcgpu_shutdown(nfcgpu_ctx *ctx)
       (void)hipFree(ctx->tapScratch);
    if (ctx->tapCount)
       (void)hipHostFree(ctx->tapCount);
+   if (ctx->tapReduceScratch)
+      (void)hipFree(ctx->tapReduceScratch);
    for (nfcgpu_ctx::StageSlot &slot: ctx->stage)
    {
       if (slot.d)
@@ -4891,14 +4921,11 @@ void nfcgpu_tap_state_init(nfcgpu_tap_state *s)
    s->clock = 0xFFFFFFFFu;
 }
 
-int nfcgpu_signal_tap(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, uint32_t stride, uint32_t format,
-                      const nfcgpu_tap_params *params, const nfcgpu_tap_state *stateIn, float *out, uint64_t outPitch, uint64_t planePitch,
-                      nfcgpu_tap_state *stateOut, nfcgpu_tap_report *report, uint32_t location)
+/* What nfcgpu_signal_tap and nfcgpu_signal_tap_reduce refuse alike, in the order the tap checks it: the parameters and the input
+ * ahead of the tap's own checks of its planes, the states and the rate behind them. */
+static int tap_check_input(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, uint32_t stride, uint32_t format,
+                           const nfcgpu_tap_params *params, uint32_t location)
 {
-   SETTLE_FIRST(ctx);
-
-   if (!ctx)
-      return NFCGPU_EINVAL;
    if (!params)
       return fail(ctx, NFCGPU_EINVAL, "tap: params is NULL");
    if (params->channels == 0 || (params->channels & ~NFC_TAP_ALL))
@@ -4914,31 +4941,61 @@ int nfcgpu_signal_tap(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_
    if (params->chunk_samples % 64u)
       return fail(ctx, NFCGPU_EINVAL, "tap: chunk_samples is not a multiple of 64");
 
-   const uint32_t layout = stride | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u);
-   const uint64_t sampleBytes = nfc_sample_bytes(layout);
-   const uint32_t planes = nfc_tap_planes(params->channels);
-   const uint64_t planeBytes = (uint64_t)n * 4u;
+   const uint64_t sampleBytes = nfc_sample_bytes(stride | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u));
 
    if (!in || ((uintptr_t)in % sampleBytes))
       return fail(ctx, NFCGPU_EINVAL, "tap: in is NULL or not aligned to a sample");
    if ((inPitch % sampleBytes) || (nBuffers > 1 && inPitch < (uint64_t)n * sampleBytes))
       return fail(ctx, NFCGPU_EINVAL, "tap: in_pitch_bytes is not a multiple of a sample or smaller than a row");
-   if (!out || ((uintptr_t)out & 3))
-      return fail(ctx, NFCGPU_EINVAL, "tap: out is NULL or not 4-byte aligned");
-   if ((planePitch % 16u) || planePitch < planeBytes)
-      return fail(ctx, NFCGPU_EINVAL, "tap: plane_pitch_bytes is not a multiple of 16 or smaller than a plane");
-   if ((outPitch % 16u) || (nBuffers > 1 && outPitch < (uint64_t)(planes - 1) * planePitch + planeBytes))
-      return fail(ctx, NFCGPU_EINVAL, "tap: out_pitch_bytes is not a multiple of 16 or smaller than the planes of a buffer");
+
+   return NFCGPU_OK;
+}
+
+static int tap_check_states_and_rate(nfcgpu_ctx *ctx, const nfcgpu_tap_params *params, const nfcgpu_tap_state *stateIn, const nfcgpu_tap_state *stateOut, NfcConfig &cfg)
+{
    if (((uintptr_t)stateIn & 3) || ((uintptr_t)stateOut & 3))
       return fail(ctx, NFCGPU_EINVAL, "tap: state_in or state_out is not 4-byte aligned");
    if (params->sample_rate == 0)
       return fail(ctx, NFCGPU_EINVAL, "tap: sample rate must be non-zero");
 
    NfcHostParams hp;
-   NfcConfig cfg;
    hp.sampleRate = params->sample_rate;
    if (!nfc_build_config(hp, cfg))
       return fail(ctx, NFCGPU_ERATE, "tap: sample rate not decodable with the fixed history depth");
+
+   return NFCGPU_OK;
+}
+
+int nfcgpu_signal_tap(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, uint32_t stride, uint32_t format,
+                      const nfcgpu_tap_params *params, const nfcgpu_tap_state *stateIn, float *out, uint64_t outPitch, uint64_t planePitch,
+                      nfcgpu_tap_state *stateOut, nfcgpu_tap_report *report, uint32_t location)
+{
+   SETTLE_FIRST(ctx);
+
+   if (!ctx)
+      return NFCGPU_EINVAL;
+
+   int rc = tap_check_input(ctx, in, inPitch, nBuffers, n, stride, format, params, location);
+   if (rc)
+      return rc;
+
+   const uint32_t layout = stride | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u);
+   const uint64_t sampleBytes = nfc_sample_bytes(layout);
+   const uint32_t planes = nfc_tap_planes(params->channels);
+   const uint64_t planeBytes = (uint64_t)n * 4u;
+
+   if (!out || ((uintptr_t)out & 3))
+      return fail(ctx, NFCGPU_EINVAL, "tap: out is NULL or not 4-byte aligned");
+   if ((planePitch % 16u) || planePitch < planeBytes)
+      return fail(ctx, NFCGPU_EINVAL, "tap: plane_pitch_bytes is not a multiple of 16 or smaller than a plane");
+   if ((outPitch % 16u) || (nBuffers > 1 && outPitch < (uint64_t)(planes - 1) * planePitch + planeBytes))
+      return fail(ctx, NFCGPU_EINVAL, "tap: out_pitch_bytes is not a multiple of 16 or smaller than the planes of a buffer");
+
+   NfcConfig cfg;
+
+   rc = tap_check_states_and_rate(ctx, params, stateIn, stateOut, cfg);
+   if (rc)
+      return rc;
 
    if (report)
       std::memset(report, 0, sizeof(*report));
@@ -5169,6 +5226,317 @@ int nfcgpu_signal_tap(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_
       report->rounds = rounds;
       report->rewalked_chunks = (uint32_t)(rewalked > 0xFFFFFFFFull ? 0xFFFFFFFFull : rewalked);
    }
+
+   return NFCGPU_OK;
+}
+
+/* ---- nfcgpu_signal_tap_reduce: the tap over slabs of whole buffers into planes the context owns, every slab reduced over the
+ * ranges that lie in it (nfc_tap_reduce.hpp) ---- */
+
+static_assert(sizeof(nfcgpu_tap_range) == sizeof(NfcTapRange) && sizeof(NfcTapRange) == 16, "a tap range is 16 bytes");
+static_assert(sizeof(nfcgpu_tap_stat) == sizeof(NfcTapStat) && sizeof(NfcTapStat) == 32 && sizeof(NfcTapPartial) == 32, "a tap record and a partial are 32 bytes");
+
+constexpr uint64_t kTapReduceBlocks = 8192;          /* of four waves: some waves per SIMD, the rest of the units by stride */
+
+int nfcgpu_signal_tap_reduce(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, uint32_t nBuffers, uint32_t n, uint32_t stride, uint32_t format,
+                             const nfcgpu_tap_params *tap, const nfcgpu_tap_reduce_params *reduce, const nfcgpu_tap_state *stateIn,
+                             const nfcgpu_tap_range *ranges, uint32_t nRanges, nfcgpu_tap_stat *out, nfcgpu_tap_state *stateOut,
+                             nfcgpu_tap_report *report, uint32_t location)
+{
+   SETTLE_FIRST(ctx);
+
+   if (!ctx)
+      return NFCGPU_EINVAL;
+
+   int rc = tap_check_input(ctx, in, inPitch, nBuffers, n, stride, format, tap, location);
+   if (rc)
+      return rc;
+
+   if (!reduce)
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: reduce is NULL");
+   if (reduce->reserved0 | reduce->reserved[0] | reduce->reserved[1] | reduce->reserved[2] | reduce->reserved[3])
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: reserved fields of reduce are not zero");
+   if (!ranges && nRanges != 0)
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: ranges is NULL and n_ranges is not 0");
+   if (!ranges && reduce->bin_samples == 0)
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: neither ranges nor bin_samples");
+   if (((uintptr_t)out & 3) || ((uintptr_t)ranges & 3))
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: out or ranges is not 4-byte aligned");
+
+   NfcConfig cfg;
+
+   rc = tap_check_states_and_rate(ctx, tap, stateIn, stateOut, cfg);
+   if (rc)
+      return rc;
+
+   const bool host = location == NFCGPU_LOC_HOST;
+   const uint32_t K = nfc_tap_planes(tap->channels);
+   const uint32_t bin = reduce->bin_samples;
+   const uint32_t bins = ranges ? 0u : (uint32_t)(((uint64_t)n + bin - 1) / bin);
+   const uint64_t nRecordRanges = ranges ? (uint64_t)nRanges : (uint64_t)nBuffers * bins;
+
+   if (nRecordRanges * K > 0xFFFFFFFFull)
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: more than 2^32 - 1 records");
+   if (nRecordRanges && !out)
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: out is NULL");
+
+   auto range_ok = [&](const NfcTapRange &g) { return g.buffer < nBuffers && g.reserved == 0 && g.first <= n && g.count <= n - g.first; };
+
+   if (host && nBuffers)
+   {
+      for (uint32_t r = 0; r < nRanges; r++)
+      {
+         if (!range_ok(reinterpret_cast<const NfcTapRange *>(ranges)[r]))
+         {
+            const std::string what = "tap reduce: range " + std::to_string(r) + " is not inside the buffers (buffer, first + count) or its reserved field is not zero";
+            return fail(ctx, NFCGPU_EINVAL, what.c_str());
+         }
+      }
+   }
+
+   if (report)
+      std::memset(report, 0, sizeof(*report));
+
+   HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+   if (nBuffers == 0)
+      return NFCGPU_OK;
+
+   const size_t records = (size_t)(nRecordRanges * K);
+   const size_t stateBytes = (size_t)nBuffers * sizeof(NfcTapRecord);
+   const size_t rangesBytes = (size_t)nRanges * sizeof(NfcTapRange);
+   const uint32_t layout = stride | (format == NFCGPU_FMT_I16 ? NFC_SAMPLE_I16 : 0u);
+   const size_t rowBytes = (size_t)n * nfc_sample_bytes(layout);
+   auto round16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+
+   /* the ranges as the host sees them, for the plan alone: device ranges are copied down, the kernels check them where they lie */
+   std::vector<NfcTapRange> copied;
+   const NfcTapRange *seen = reinterpret_cast<const NfcTapRange *>(ranges);
+
+   if (!host && nRanges)
+   {
+      copied.resize(nRanges);
+      HIP_TRY(ctx, hipMemcpyAsync(copied.data(), ranges, rangesBytes, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      seen = copied.data();
+   }
+
+   /* the plan: the ranges by buffer (what is in no buffer behind them all), the segments ahead of each, every segment by name */
+   std::vector<uint32_t> order(nRanges), keys(nRanges);
+   std::vector<uint64_t> prefix((size_t)nRanges + 1, 0);
+   std::vector<NfcTapSegment> table;
+
+   if (ranges)
+   {
+      auto key = [&](uint32_t r) { return seen[r].buffer < nBuffers ? seen[r].buffer : nBuffers; };
+
+      for (uint32_t r = 0; r < nRanges; r++)
+         order[r] = r;
+      if (!std::is_sorted(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); }))
+         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+      for (uint32_t o = 0; o < nRanges; o++)
+      {
+         keys[o] = key(order[o]);
+         prefix[o + 1] = prefix[o] + (range_ok(seen[order[o]]) ? nfc_tap_segments(seen[order[o]].count) : 0u);
+      }
+
+      table.reserve((size_t)prefix[nRanges]);
+      for (uint32_t o = 0; o < nRanges; o++)
+         for (uint32_t s = 0; s < (uint32_t)(prefix[o + 1] - prefix[o]); s++)
+            table.push_back(NfcTapSegment {order[o], s});
+   }
+
+   const uint32_t segsPerBin = ranges ? 0u : nfc_tap_segments(bin < n ? bin : n);
+
+   /* the items and the segments of the slab b0 ... b1 - 1 */
+   auto slab_plan = [&](uint32_t b0, uint32_t b1, uint64_t &firstItem, uint64_t &items, uint64_t &segments) {
+      if (!ranges)
+      {
+         firstItem = (uint64_t)b0 * bins;
+         items = (uint64_t)(b1 - b0) * bins;
+         segments = items * segsPerBin;
+         return;
+      }
+      const uint64_t o0 = std::lower_bound(keys.begin(), keys.end(), b0) - keys.begin();
+      const uint64_t o1 = b1 == nBuffers ? nRanges : (uint64_t)(std::lower_bound(keys.begin(), keys.end(), b1) - keys.begin());
+      firstItem = o0;
+      items = o1 - o0;
+      segments = prefix[o1] - prefix[o0];
+   };
+
+   const uint64_t planePitch = std::max<uint64_t>(((uint64_t)n * 4u + 255) & ~(uint64_t)255, 256);
+   const uint64_t bufferPitch = planePitch * K;
+
+   /* scratch_bytes == 0: every slab pays the tap's rounds anew, so all the planes at once where three quarters of
+    * the device memory that is free (this call's scratch of before counted as free) hold them */
+   uint64_t wanted = reduce->scratch_bytes;
+
+   if (!wanted)
+   {
+      size_t freeBytes = 0, totalBytes = 0;
+
+      HIP_TRY(ctx, hipMemGetInfo(&freeBytes, &totalBytes));
+      wanted = totalBytes ? ((uint64_t)freeBytes + ctx->tapReduceScratchBytes) / 4 * 3 : ~0ull;
+   }
+
+   const uint32_t slabBuffers = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(wanted / bufferPitch, 1), nBuffers);
+
+   uint64_t mostSegments = 0;
+
+   for (uint64_t b0 = 0; b0 < nBuffers; b0 += slabBuffers)
+   {
+      uint64_t firstItem, items, segments;
+      slab_plan((uint32_t)b0, (uint32_t)std::min<uint64_t>(b0 + slabBuffers, nBuffers), firstItem, items, segments);
+      mostSegments = std::max(mostSegments, segments);
+   }
+
+   const size_t planesBytes = (size_t)(bufferPitch * slabBuffers);
+   const size_t need = planesBytes + (size_t)mostSegments * K * sizeof(NfcTapPartial);
+
+   if (need > ctx->tapReduceScratchBytes)
+   {
+      if (ctx->tapReduceScratch)
+         (void)hipFree(ctx->tapReduceScratch);
+      ctx->tapReduceScratch = nullptr;
+      ctx->tapReduceScratchBytes = 0;
+      if (hipMalloc(&ctx->tapReduceScratch, need) != hipSuccess)
+         return fail(ctx, NFCGPU_ENOMEM, "tap reduce: scratch for the planes and the partials could not be allocated");
+      ctx->tapReduceScratchBytes = need;
+   }
+
+   /* up: rows and state_in (host memory), the caller's ranges (host memory), the plan (order, prefix, table). down: the flag word; records and state_out
+    * (host memory) */
+   nfcgpu_ctx::StageSlot *up = nullptr, *down = nullptr;
+
+   struct Release
+   {
+      nfcgpu_ctx *ctx;
+      nfcgpu_ctx::StageSlot **up, **down;
+      ~Release()
+      {
+         if (*up)
+            stage_release(ctx, *up);
+         if (*down)
+            stage_release(ctx, *down);
+      }
+   } release {ctx, &up, &down};
+
+   const size_t upPitch = (rowBytes + 255) & ~(size_t)255;
+   const size_t rowsAt = 0, statesAt = rowsAt + (host ? upPitch * nBuffers : 0), rangesAt = statesAt + (host ? stateBytes : 0);
+   const size_t orderAt = rangesAt + (host ? rangesBytes : 0), prefixAt = orderAt + round16((size_t)nRanges * 4u);
+   const size_t tableAt = prefixAt + ((size_t)nRanges + 1) * 8u;
+   const size_t upBytes = tableAt + table.size() * sizeof(NfcTapSegment) + 8;
+   const size_t flagAt = 0, recordsAt = 16, statesOutAt = recordsAt + (host ? records * sizeof(NfcTapStat) : 0);
+   const size_t downBytes = statesOutAt + (host ? stateBytes : 0);
+
+   ctx->inflight = true;
+
+   rc = stage_acquire(ctx, upBytes, &up);
+   if (rc)
+      return rc;
+   rc = stage_acquire(ctx, downBytes, &down);
+   if (rc)
+      return rc;
+
+   if (host)
+   {
+      for (uint32_t b = 0; b < nBuffers; b++)
+         std::memcpy(up->h + rowsAt + (size_t)b * upPitch, (const uint8_t *)in + (size_t)b * inPitch, rowBytes);
+      if (stateIn)
+         std::memcpy(up->h + statesAt, stateIn, stateBytes);
+      if (nRanges)
+         std::memcpy(up->h + rangesAt, ranges, rangesBytes);
+   }
+   if (nRanges)
+      std::memcpy(up->h + orderAt, order.data(), (size_t)nRanges * 4u);
+   std::memcpy(up->h + prefixAt, prefix.data(), ((size_t)nRanges + 1) * 8u);
+   if (!table.empty())
+      std::memcpy(up->h + tableAt, table.data(), table.size() * sizeof(NfcTapSegment));
+
+   HIP_TRY(ctx, hipMemcpyAsync(up->d, up->h, upBytes, hipMemcpyHostToDevice, ctx->stream));
+   HIP_TRY(ctx, hipMemsetAsync(down->d + flagAt, 0, 16, ctx->stream));
+
+   const uint8_t *dIn = host ? up->d + rowsAt : (const uint8_t *)in;
+   const uint64_t dInPitch = host ? upPitch : inPitch;
+   const NfcTapRecord *dStateIn = !stateIn ? nullptr : (host ? (const NfcTapRecord *)(up->d + statesAt) : (const NfcTapRecord *)stateIn);
+   NfcTapRecord *dStateOut = !stateOut ? nullptr : (host ? (NfcTapRecord *)(down->d + statesOutAt) : (NfcTapRecord *)stateOut);
+
+   NfcTapReduceArgs A;
+   std::memset(&A, 0, sizeof(A));
+
+   A.planes = (const float *)ctx->tapReduceScratch;
+   A.partials = (NfcTapPartial *)((uint8_t *)ctx->tapReduceScratch + planesBytes);
+   A.ranges = !ranges ? nullptr : (host ? (const NfcTapRange *)(up->d + rangesAt) : (const NfcTapRange *)ranges);
+   A.order = (const uint32_t *)(up->d + orderAt);
+   A.prefix = (const uint64_t *)(up->d + prefixAt);
+   A.table = (const NfcTapSegment *)(up->d + tableAt);
+   A.out = host ? (NfcTapStat *)(down->d + recordsAt) : (NfcTapStat *)out;
+   A.flag = (uint32_t *)(down->d + flagAt);
+   A.bufferPitch = bufferPitch;
+   A.planePitch = planePitch;
+   A.n = n;
+   A.nBuffers = nBuffers;
+   A.channels = K;
+   A.binSamples = bin;
+   A.bins = bins;
+   A.segsPerBin = segsPerBin;
+
+   nfcgpu_tap_report sum;
+   std::memset(&sum, 0, sizeof(sum));
+
+   for (uint64_t b0 = 0; b0 < nBuffers; b0 += slabBuffers)
+   {
+      const uint32_t b1 = (uint32_t)std::min<uint64_t>(b0 + slabBuffers, nBuffers);
+      nfcgpu_tap_report one;
+      uint64_t segments;
+
+      /* stage 1: the slab's planes, by the tap itself (it returns when they are complete) */
+      rc = nfcgpu_signal_tap(ctx, dIn + b0 * dInPitch, dInPitch, b1 - (uint32_t)b0, n, stride, format, tap, (const nfcgpu_tap_state *)(dStateIn ? dStateIn + b0 : nullptr),
+                             (float *)ctx->tapReduceScratch, bufferPitch, planePitch, (nfcgpu_tap_state *)(dStateOut ? dStateOut + b0 : nullptr), &one, NFCGPU_LOC_DEVICE);
+      if (rc)
+         return rc;
+
+      sum.chunks += one.chunks;
+      sum.rounds += one.rounds;
+      sum.rewalked_chunks += one.rewalked_chunks;
+
+      /* stage 2: the ranges of the slab */
+      A.b0 = (uint32_t)b0;
+      A.b1 = b1;
+      slab_plan(A.b0, A.b1, A.firstItem, A.items, segments);
+      A.units = segments * K;
+      A.prefix0 = ranges ? prefix[(size_t)A.firstItem] : 0;
+
+      if (A.units)
+      {
+         const uint64_t blocks = (A.units + NfcTapReduceShape::kWaves - 1) / NfcTapReduceShape::kWaves;
+         hipLaunchKernelGGL(nfc_tap_reduce_kernel, dim3((uint32_t)std::min(blocks, kTapReduceBlocks)), dim3(64 * NfcTapReduceShape::kWaves), 0, ctx->stream, A);
+         HIP_TRY(ctx, hipGetLastError());
+      }
+      if (A.items)
+      {
+         const uint64_t blocks = (A.items * K + 255) / 256;
+         hipLaunchKernelGGL(nfc_tap_reduce_finish_kernel, dim3((uint32_t)std::min<uint64_t>(blocks, 65536)), dim3(256), 0, ctx->stream, A);
+         HIP_TRY(ctx, hipGetLastError());
+      }
+   }
+
+   HIP_TRY(ctx, hipMemcpyAsync(down->h, down->d, downBytes, hipMemcpyDeviceToHost, ctx->stream));
+   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+   if (host)
+   {
+      if (records)
+         std::memcpy(out, down->h + recordsAt, records * sizeof(NfcTapStat));
+      if (stateOut)
+         std::memcpy(stateOut, down->h + statesOutAt, stateBytes);
+   }
+
+   if (report)
+      *report = sum;
+
+   if (*(const uint32_t *)(down->h + flagAt))
+      return fail(ctx, NFCGPU_EINVAL, "tap reduce: a range in device memory is not inside the buffers or its reserved field is not zero; its records are empty");
 
    return NFCGPU_OK;
 }

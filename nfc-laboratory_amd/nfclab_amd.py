@@ -32,6 +32,11 @@ TAP_NAMES = ("value", "filtered", "deviation", "average", "envelope", "depth")
 TAP_STATE_DTYPE = np.dtype([("clock", np.uint32), ("pulse_filter", np.uint32), ("envelope", np.float32), ("filter_n1", np.float32),
                             ("deviation", np.float32), ("average", np.float32), ("reserved", np.uint32, (2,))])
 
+# nfcgpu_signal_tap_reduce: one nfcgpu_tap_range per range, one nfcgpu_tap_stat per range and selected channel
+TAP_RANGE_DTYPE = np.dtype([("buffer", np.uint32), ("first", np.uint32), ("count", np.uint32), ("reserved", np.uint32)])
+TAP_STAT_DTYPE = np.dtype([("min", np.float32), ("max", np.float32), ("mean", np.float32), ("valid", np.uint32), ("argmin", np.uint32),
+                           ("argmax", np.uint32), ("reserved", np.uint32, (2,))])
+
 FRAME_CARRIER_OFF, FRAME_CARRIER_ON, FRAME_POLL, FRAME_LISTEN = 0x100, 0x101, 0x102, 0x103
 
 
@@ -143,6 +148,15 @@ class TapReport(ctypes.Structure):
     ]
 
 
+class TapReduceParams(ctypes.Structure):
+    _fields_ = [
+        ("bin_samples", ctypes.c_uint32),
+        ("reserved0", ctypes.c_uint32),
+        ("scratch_bytes", ctypes.c_uint64),
+        ("reserved", ctypes.c_uint32 * 4),
+    ]
+
+
 # the reference's window names (FourierProcessTask.cpp:121-143; see include/nfcgpu.h for what they compute)
 WINDOWS = {"none": 0, "hamming": 1, "hann": 2}
 
@@ -201,6 +215,7 @@ def load_library(path=LIB_PATH):
     lib.nfcgpu_tap_state_init.restype = None
     lib.nfcgpu_signal_tap.argtypes = [vp, vp, u64, u32, u32, u32, u32, P(TapParams), vp, vp, u64, u64, vp, P(TapReport), u32]
     lib.nfcgpu_stream_tap_state.argtypes = [vp, u32, vp]
+    lib.nfcgpu_signal_tap_reduce.argtypes = [vp, vp, u64, u32, u32, u32, u32, P(TapParams), P(TapReduceParams), vp, vp, u32, vp, vp, P(TapReport), u32]
     lib.nfcgpu_wav_write.argtypes = [ctypes.c_char_p, vp, u64, u32, u32, u32, vp]
     lib.nfcgpu_wav_append.argtypes = [ctypes.c_char_p, vp, u64]
     lib.nfcgpu_flush.argtypes = [vp, u32]
@@ -267,6 +282,34 @@ def wav_append(path, pcm):
     if channels == 0 or pcm.size % channels:
         raise NfcGpuError(-1, "not a capture file, or samples that do not fill its channels")
     _wav_check(load_library().nfcgpu_wav_append(os.fsencode(path), pcm.ctypes.data, pcm.size // channels))
+
+
+def as_tap_ranges(ranges):
+    """TAP_RANGE_DTYPE [n] of such an array or of rows (buffer, first, count)."""
+    if isinstance(ranges, np.ndarray) and ranges.dtype == TAP_RANGE_DTYPE:
+        return np.ascontiguousarray(ranges).reshape(-1)
+    rows = np.asarray(ranges, dtype=np.uint32).reshape(-1, 3)
+    out = np.zeros(rows.shape[0], dtype=TAP_RANGE_DTYPE)
+    out["buffer"], out["first"], out["count"] = rows[:, 0], rows[:, 1], rows[:, 2]
+    return out
+
+
+def frame_ranges(frames, state, n_samples, buffer=0):
+    """Decoded frames (the tuples of NfcGpu.poll) as ranges of a buffer of n_samples samples tapped from `state`
+    (TAP_STATE_DTYPE [1], as NfcGpu.stream_tap_state gave it before the buffer was submitted): (TAP_RANGE_DTYPE [kept], the indices
+    into `frames` of the frames kept). Sample i of the buffer has the clock state.clock + 1 + i (32-bit), the number a frame's
+    sample_start and sample_end carry. sample_end is taken as inclusive: it is the clock of the sample at which the frame's last
+    symbol ends (a carrier frame has sample_start == sample_end and gives a range of one sample). A frame is clipped to the
+    buffer; a frame that lies outside it altogether is dropped."""
+    clock0 = (int(np.asarray(state)["clock"].reshape(-1)[0]) + 1) & 0xFFFFFFFF
+    ranges, kept = [], []
+    for at, frame in enumerate(frames):
+        first, last = ((int(v) - clock0 + 0x80000000) % 0x100000000 - 0x80000000 for v in (frame[5], frame[6]))
+        first, last = max(first, 0), min(last, n_samples - 1)
+        if first <= last:
+            ranges.append((buffer, first, last - first + 1))
+            kept.append(at)
+    return as_tap_ranges(ranges), np.array(kept, dtype=np.int64)
 
 
 class NfcGpu:
@@ -487,6 +530,44 @@ class NfcGpu:
         report = TapReport()
         self._check(self.lib.nfcgpu_signal_tap(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, stride, fmt, ctypes.byref(p), state_in_ptr,
                                                out_ptr, out_pitch_bytes, plane_pitch_bytes, state_out_ptr, ctypes.byref(report), LOC_DEVICE))
+        return report
+
+    def signal_tap_reduce(self, buffers, sample_rate, channels=TAP_ALL, ranges=None, bin_samples=0, stride=1, fmt=FMT_F32, state=None,
+                          chunk=0, warm=0, scratch_bytes=0, with_state=False):
+        """The tap's channels reduced over sample ranges (nfcgpu_signal_tap_reduce) of a 2-D array [n_buffers, n * stride] in host
+        memory: TAP_STAT_DTYPE [n_ranges, K], K the channels selected, in bit order. ranges: TAP_RANGE_DTYPE [n_ranges] (or rows
+        of buffer, first, count), or None: every buffer in bins of bin_samples, range r = buffer r // bins, bin r % bins.
+        scratch_bytes bounds the planes held on the device at a time (0: the library's choice). with_state: (records,
+        TAP_STATE_DTYPE [n_buffers] behind the last sample, TapReport)."""
+        buffers = np.ascontiguousarray(buffers, dtype=np.int16 if fmt == FMT_I16 else np.float32)
+        nb, width = buffers.shape
+        assert width % stride == 0
+        n = width // stride
+        k = bin(channels & TAP_ALL).count("1")
+        if ranges is None:
+            n_ranges, rp = nb * (-(-n // bin_samples) if bin_samples else 0), None
+        else:
+            ranges = as_tap_ranges(ranges)
+            n_ranges, rp = ranges.shape[0], ranges.ctypes.data
+        if state is not None:
+            state = np.ascontiguousarray(state, dtype=TAP_STATE_DTYPE)
+            assert state.shape == (nb,)
+        out = np.zeros((n_ranges, max(k, 1)), dtype=TAP_STAT_DTYPE)
+        states = np.zeros(nb, dtype=TAP_STATE_DTYPE)
+        p, q, report = TapParams(sample_rate, channels, chunk, warm), TapReduceParams(bin_samples, 0, scratch_bytes), TapReport()
+        self._check(self.lib.nfcgpu_signal_tap_reduce(self.ctx, buffers.ctypes.data, width * buffers.itemsize, nb, n, stride, fmt, ctypes.byref(p),
+                                                      ctypes.byref(q), None if state is None else state.ctypes.data, rp,
+                                                      0 if ranges is None else n_ranges, out.ctypes.data, states.ctypes.data, ctypes.byref(report), LOC_HOST))
+        return (out, states, report) if with_state else out
+
+    def signal_tap_reduce_device(self, in_ptr, in_pitch_bytes, n_buffers, n_samples, sample_rate, out_ptr, channels=TAP_ALL, ranges_ptr=None,
+                                 n_ranges=0, bin_samples=0, stride=1, fmt=FMT_F32, state_in_ptr=None, state_out_ptr=None, chunk=0, warm=0,
+                                 scratch_bytes=0):
+        """Same with device pointers (samples, ranges, records and states resident in HBM); returns the TapReport. A range that is
+        not inside the buffers gets the empty record and the call raises NfcGpuError (NFCGPU_EINVAL) with the other records complete."""
+        p, q, report = TapParams(sample_rate, channels, chunk, warm), TapReduceParams(bin_samples, 0, scratch_bytes), TapReport()
+        self._check(self.lib.nfcgpu_signal_tap_reduce(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, stride, fmt, ctypes.byref(p), ctypes.byref(q),
+                                                      state_in_ptr, ranges_ptr, n_ranges, out_ptr, state_out_ptr, ctypes.byref(report), LOC_DEVICE))
         return report
 
     def stream_tap_state(self, stream):
