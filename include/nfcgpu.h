@@ -469,6 +469,67 @@ int nfcgpu_signal_tap_reduce(nfcgpu_ctx *ctx, const void *in, uint64_t in_pitch_
                              nfcgpu_tap_stat *out /* records */, nfcgpu_tap_state *state_out /* n_buffers, may be NULL */,
                              nfcgpu_tap_report *report /* host memory, may be NULL */, uint32_t location);
 
+/* The signal of a trace file: the control points nfcgpu_resample_radio[_fmt] leaves in memory, delta-coded into the
+ * "radio-<id>.apcm" entries the reference's TraceStorageTask stores beside frame.json (writeRadioEntry,
+ * lab-tasks/src/main/cpp/tasks/TraceStorageTask.cpp:881-1003; read back by readRadioEntry :760-879) - what its signal view draws
+ * when the trace is opened. nfcgpu_trace_write_signal puts the entries into the archive.
+ *
+ * Input: the rows exactly as the resampler writes them - buffer b holds counts[b] float pairs (value, offset in buffer) at
+ * pairs + b * pairs_pitch_bytes (`pairs` and the pitch 8-byte aligned, the pitch at least capacity_pairs pairs; capacity_pairs
+ * bounds a row). buffers_per_entry = G consecutive buffers are one entry: n_buffers is a multiple of G, entry e is the buffers
+ * e * G ... e * G + G - 1 and carries the stream id first_stream_id + e. Buffer j of an entry has the stream position
+ * first_position + j * buffer_samples (hw::SignalBuffer::offset()). `location` applies to pairs, counts, out and info.
+ *
+ * What an entry is. sampleStart = (uint32)(sample_rate * range_start), sampleEnd = (uint32)(sample_rate * range_end): the
+ * reference's double product and cast (:907-908). range_start == range_end == 0 means every point (sampleEnd = 2^32 - 1): the
+ * departure from the reference nfcgpu_trace_write_frames makes for frames, for the same reason. Point by point, in buffer order
+ * and then in pair order (:957-970):
+ *   offset = position + (uint32)pair.offset (a negative value or a NaN gives 0, the cast saturates above);
+ *   sample = the quantiser of nfcgpu_record: static_cast<short>(value * 32768.0f) in range (:969), saturated beyond it, a NaN as
+ *            0 - that call's documented departure.
+ * A point is kept iff sampleStart <= offset <= sampleEnd. For the monotone offsets the resampler produces this is the reference's
+ * `continue` below the range and `break` above it (:972-976). Kept point k becomes three bytes (:979-981): (offset_k -
+ * offset_{k-1}) & 0xff, then (sample_k - sample_{k-1}) & 0xffff, low byte first, with offset_{-1} = sampleStart and sample_{-1}
+ * = 0 (:953-954). The entry is the 32-byte SampleHdr (:55-60, indices :36-39) - "APCM", version 2, info = {0, 0 (start offset:
+ * the reference writes 0), K, stream id, sample_rate, 0} - followed by the K records. Entry e is written at out + e *
+ * out_pitch_bytes (`out` and the pitch multiples of 4); bytes of a pitch beyond the entry are left alone. An entry has the same
+ * bytes on every run.
+ *
+ * Results, one per entry: bytes = 32 + 3 K, records = K, wrapped = the records whose offset delta (mod 2^32) was above 255 - the
+ * reference loses those silently; it is 0 for resampler output of consecutive buffers with a range inside the data (a point at
+ * least every 255 samples). An entry of more than capacity_bytes gets its header, with the number of records that are there in
+ * info[2], and the records that fit whole; K is still counted and the call returns NFCGPU_EOVERFLOW, as nfcgpu_resample_radio
+ * does. An entry with no kept point is a bare header. n_buffers == 0 is success. nfcgpu_apcm_bound(total_pairs) = 32 + 3 *
+ * total_pairs is the size of an entry that keeps total_pairs points.
+ *
+ * NFCGPU_EINVAL: a NULL context, params or (with n_buffers > 0) pairs, counts, out or info; reserved fields that are not zero; a
+ * location that is not one of the two; sample_rate 0; buffers_per_entry 0 or not dividing n_buffers; first_position +
+ * buffers_per_entry * buffer_samples (the position of the last buffer's end) not below 2^32; first_stream_id + n_buffers /
+ * buffers_per_entry above 2^32; a range that is not 0 <= range_start <= range_end (a NaN is none) or with sample_rate * range_end
+ * not below 2^32; pointers or pitches not aligned as above (counts and info: 4 bytes); pairs_pitch_bytes below capacity_pairs
+ * pairs; capacity_bytes below 32 or above out_pitch_bytes; buffers_per_entry * capacity_pairs pairs needing 4 GiB or more. A
+ * counts[b] above capacity_pairs in host memory is refused before anything runs; in device memory the kernels read capacity_pairs
+ * pairs of that buffer and no more, every entry is complete, and the call returns NFCGPU_EINVAL - the rule
+ * nfcgpu_signal_tap_reduce has for ranges. */
+typedef struct nfcgpu_apcm_params {
+   uint32_t sample_rate;        /* Hz: goes into the header and turns the range into samples */
+   uint32_t buffers_per_entry;  /* G */
+   uint32_t buffer_samples;     /* samples a buffer stands for: the step of the stream position from one buffer to the next */
+   uint32_t first_stream_id;    /* entry e carries first_stream_id + e */
+   uint32_t first_position;     /* stream position of the first buffer of every entry */
+   uint32_t reserved0;          /* zero */
+   double range_start, range_end; /* seconds; 0, 0 = every point */
+   uint32_t reserved[4];        /* zero */
+} nfcgpu_apcm_params;
+
+typedef struct nfcgpu_apcm_info { uint32_t bytes, records, wrapped, reserved; } nfcgpu_apcm_info;   /* one per entry, 16 bytes */
+
+uint64_t nfcgpu_apcm_bound(uint64_t total_pairs);
+
+int nfcgpu_apcm_encode(nfcgpu_ctx *ctx, const float *pairs, uint64_t pairs_pitch_bytes, const uint32_t *counts, uint32_t n_buffers,
+                       uint32_t capacity_pairs, const nfcgpu_apcm_params *params, void *out, uint64_t out_pitch_bytes,
+                       uint64_t capacity_bytes, nfcgpu_apcm_info *info, uint32_t location);
+
 /* Capture files as hw::RecordDevice writes them (RecordDevice.cpp:493-546, structures :53-100), host only, no context and
  * no device: a 92-byte header - RIFF / WAVE; "fmt " (16: PCM 1, channels, rate, byte rate, block align, 16 bits); "META" (40:
  * "meta", epoch = stream_time, keys[8], the first `channels` taken from `keys`, NULL = zeros); "data" - then the samples,
@@ -507,6 +568,17 @@ int nfcgpu_pending(nfcgpu_ctx *ctx, uint32_t stream_id, uint32_t *count);
 int nfcgpu_trace_write_frames(const char *path, const nfcgpu_frame *frames, uint32_t count, int64_t stream_time, double range_start, double range_end,
                               uint32_t *written);
 int nfcgpu_trace_write(nfcgpu_ctx *ctx, uint32_t stream_id, const char *path, double range_start, double range_end, uint32_t *written);
+/* A trace with the signal: frame.json exactly as nfcgpu_trace_write_frames writes it for the same arguments, then one entry
+ * "radio-<id>.apcm" per APCM entry (nfcgpu_apcm_encode; host memory), in the order given - the order and the names of
+ * writeTraceFile / writeRadioData (TraceStorageTask.cpp:322-364, :1032-1057); <id> is the stream id in the entry's header.
+ * entries[i] points to entry_bytes[i] bytes. Host only, no context and no device. With n_entries == 0 the file is byte for byte
+ * that of nfcgpu_trace_write_frames. The frames' range is not applied to the entries: they are encoded with theirs.
+ * NFCGPU_EINVAL, beyond that call's: entries or entry_bytes NULL with n_entries > 0; an entry that is NULL, shorter than its
+ * 32-byte header, without the magic "APCM" or with a version that is not 2; entry_bytes[i] != 32 + 3 * info[2] (what the
+ * reference's reader checks, :816-827); two entries with one id; an archive of 4 GiB or more (checked before an entry's records
+ * are read). */
+int nfcgpu_trace_write_signal(const char *path, const nfcgpu_frame *frames, uint32_t count, int64_t stream_time, double range_start, double range_end,
+                              uint32_t *written, const void *const *entries, const uint64_t *entry_bytes, uint32_t n_entries);
 
 /* device-resident view of the frames produced since the last sync: packed records of 32-bit words
  * [stream_id, tech, type, flags, phase, rate, start, end, length, payload...]; used for RCCL frame gathers */

@@ -12,8 +12,12 @@
  * [rangeStart, rangeEnd] keeps the frames inside it and shifts their times and sample numbers to its start
  * (TraceStorageTask.cpp:461-483).
  *
- * The archive is written without a compression library: a ustar header + the entry + two zero blocks, wrapped in a gzip
- * member whose deflate stream consists of stored blocks (RFC 1951 3.2.4) - any inflate reads it, the reference's included.
+ * The signal goes into the same archive behind frame.json as entries "radio-<id>.apcm", one per stream, in the order and under the
+ * names of writeTraceFile / writeRadioData (:322-364, :1032-1057): nfcgpu_trace_write_signal takes them as nfcgpu_apcm_encode made
+ * them (nfc_apcm.hpp) and admits what the reference's reader admits (readRadioEntry :789-827).
+ *
+ * The archive is written without a compression library: per entry a ustar header + the entry, then two zero blocks, wrapped in a
+ * gzip member whose deflate stream consists of stored blocks (RFC 1951 3.2.4) - any inflate reads it, the reference's included.
  */
 #include <cstdint>
 #include <cstdio>
@@ -81,17 +85,19 @@ uint32_t crc32_of(const uint8_t *p, size_t n)
    return c ^ 0xFFFFFFFFu;
 }
 
-/* one ustar entry (name, 0664, regular file) followed by the archive's end marker */
-std::vector<uint8_t> tar_of(const char *name, const std::string &content)
+/* one ustar entry (name, 0664, regular file) behind what the archive holds already */
+void tar_add(std::vector<uint8_t> &tar, const char *name, const void *content, size_t size)
 {
-   std::vector<uint8_t> tar(512, 0);
-   uint8_t *h = tar.data();
+   const size_t at = tar.size();
+
+   tar.resize(at + 512, 0);
+   uint8_t *h = tar.data() + at;
 
    std::snprintf((char *)h, 100, "%s", name);
    std::snprintf((char *)h + 100, 8, "%07o", 0664);
    std::snprintf((char *)h + 108, 8, "%07o", 0);
    std::snprintf((char *)h + 116, 8, "%07o", 0);
-   std::snprintf((char *)h + 124, 12, "%011llo", (unsigned long long)content.size());
+   std::snprintf((char *)h + 124, 12, "%011llo", (unsigned long long)size);
    std::snprintf((char *)h + 136, 12, "%011o", 0);
    std::memset(h + 148, ' ', 8);
    h[156] = '0';
@@ -106,10 +112,14 @@ std::vector<uint8_t> tar_of(const char *name, const std::string &content)
    h[154] = 0;
    h[155] = ' ';
 
-   tar.insert(tar.end(), content.begin(), content.end());
+   tar.insert(tar.end(), (const uint8_t *)content, (const uint8_t *)content + size);
    tar.resize((tar.size() + 511) / 512 * 512, 0);
+}
+
+/* the archive's end marker */
+void tar_end(std::vector<uint8_t> &tar)
+{
    tar.resize(tar.size() + 1024, 0);
-   return tar;
 }
 
 int write_gzip_stored(const char *path, const std::vector<uint8_t> &raw)
@@ -140,14 +150,9 @@ int write_gzip_stored(const char *path, const std::vector<uint8_t> &raw)
    return ok ? NFCGPU_OK : NFCGPU_EIO;
 }
 
-}
-
-extern "C" int nfcgpu_trace_write_frames(const char *path, const nfcgpu_frame *frames, uint32_t count, int64_t stream_time, double range_start, double range_end,
-                                         uint32_t *written)
+/* frame.json of the frames inside the range (0, 0: all of them); *kept = how many */
+std::string frames_json(const nfcgpu_frame *frames, uint32_t count, int64_t stream_time, double range_start, double range_end, uint32_t *keptOut)
 {
-   if (!path || (count && !frames))
-      return NFCGPU_EINVAL;
-
    const bool ranged = range_end > range_start; /* (0, 0: everything) */
    std::string json = "{\"frames\":[";
    uint32_t kept = 0;
@@ -212,10 +217,78 @@ extern "C" int nfcgpu_trace_write_frames(const char *path, const nfcgpu_frame *f
 
    json += "]}";
 
+   *keptOut = kept;
+   return json;
+}
+
+uint32_t word_at(const uint8_t *at)
+{
+   return (uint32_t)at[0] | ((uint32_t)at[1] << 8) | ((uint32_t)at[2] << 16) | ((uint32_t)at[3] << 24);
+}
+
+}
+
+extern "C" int nfcgpu_trace_write_frames(const char *path, const nfcgpu_frame *frames, uint32_t count, int64_t stream_time, double range_start, double range_end,
+                                         uint32_t *written)
+{
+   return nfcgpu_trace_write_signal(path, frames, count, stream_time, range_start, range_end, written, nullptr, nullptr, 0);
+}
+
+/* frame.json, then the APCM entries as "radio-<id>.apcm" (TraceStorageTask.cpp:322-364, :1032-1057). An entry is taken when it is
+ * what the reference's reader accepts (:789-827): the magic, version 2, a size of 32 + 3 * info[2]. */
+extern "C" int nfcgpu_trace_write_signal(const char *path, const nfcgpu_frame *frames, uint32_t count, int64_t stream_time, double range_start, double range_end,
+                                         uint32_t *written, const void *const *entries, const uint64_t *entry_bytes, uint32_t n_entries)
+{
+   if (!path || (count && !frames) || (n_entries && (!entries || !entry_bytes)))
+      return NFCGPU_EINVAL;
+
+   uint32_t kept = 0;
+   const std::string json = frames_json(frames, count, stream_time, range_start, range_end, &kept);
+
+   /* the archive's size and every header first: nothing of an entry's records is read before the archive is known to fit */
+   auto blocks = [](uint64_t bytes) { return 512 + (bytes + 511) / 512 * 512; };
+   uint64_t total = blocks(json.size()) + 1024;
+   std::vector<uint32_t> ids(n_entries);
+
+   for (uint32_t i = 0; i < n_entries; i++)
+   {
+      const uint8_t *e = (const uint8_t *)entries[i];
+
+      if (!e || entry_bytes[i] < 32 || std::memcmp(e, "APCM", 4) != 0 || word_at(e + 4) != 2 || entry_bytes[i] != 32 + 3 * (uint64_t)word_at(e + 16))
+         return NFCGPU_EINVAL;
+
+      ids[i] = word_at(e + 20);
+
+      for (uint32_t k = 0; k < i; k++)
+         if (ids[k] == ids[i])
+            return NFCGPU_EINVAL;
+
+      total += blocks(entry_bytes[i]);
+
+      if (total >= 0x100000000ull)
+         return NFCGPU_EINVAL;
+   }
+
+   if (total >= 0x100000000ull)
+      return NFCGPU_EINVAL;
+
+   std::vector<uint8_t> tar;
+   tar.reserve((size_t)total);
+   tar_add(tar, "frame.json", json.data(), json.size());
+
+   for (uint32_t i = 0; i < n_entries; i++)
+   {
+      char name[32];
+      std::snprintf(name, sizeof(name), "radio-%u.apcm", ids[i]);
+      tar_add(tar, name, entries[i], (size_t)entry_bytes[i]);
+   }
+
+   tar_end(tar);
+
    if (written)
       *written = kept;
 
-   return write_gzip_stored(path, tar_of("frame.json", json));
+   return write_gzip_stored(path, tar);
 }
 
 /* ---- capture files: the header hw::RecordDevice writes (RecordDevice.cpp:493-546, structures :53-100) and the samples behind it ---- */

@@ -40,6 +40,7 @@ static inline uint32_t tap_twin_add(uint32_t *p, uint32_t v) { const uint32_t ol
 #endif
 #include "nfc_tap.hpp"
 #include "nfc_tap_reduce.hpp"
+#include "nfc_apcm.hpp"
 
 __global__ void nfc_demod_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
 __global__ void nfc_demod_exact_kernel(const NfcConfig *__restrict__ cfgPtr, NfcLaunch L);
@@ -378,7 +379,96 @@ void nfc_tap_reduce_finish_kernel(NfcTapReduceArgs A)
    for (uint64_t t = 0; t < A.items * A.channels; t++)
       nfc_tap_reduce_finish(A, t);
 }
+
+/* ... and of the kernels of nfcgpu_apcm_encode (nfc_apcm.hip): the units and the entries of nfc_apcm.hpp as loops, a unit's points one
+ * after the other where the device takes a tile of 64 at a time, the parts merged in sequence where it scans a wave. The staging
+ * area and the way it is written out are the device's, lane by lane. */
+void nfc_apcm_count_kernel(NfcApcmArgs A)
+{
+   for (uint64_t unit = 0; unit < A.units; unit++)
+   {
+      uint32_t buffer, begin, end, position;
+
+      nfc_apcm_unit(A, unit, buffer, begin, end, position);
+
+      const NfcApcmPair *row = nfc_apcm_row(A, buffer);
+      NfcApcmPart run = nfc_apcm_none();
+
+      for (uint32_t i = begin; i < end; i++)
+      {
+         const NfcApcmPoint p = nfc_apcm_point(A, row, position, i);
+
+         if (p.keep)
+            run = nfc_apcm_merge(run, nfc_apcm_single(p));
+      }
+
+      A.parts[unit] = run;
+   }
+}
+
+void nfc_apcm_scan_kernel(NfcApcmArgs A)
+{
+   for (uint32_t entry = 0; entry < A.nEntries; entry++)
+   {
+      NfcApcmPart carry = nfc_apcm_start(A);
+
+      for (uint64_t unit = (uint64_t)entry * A.unitsPerEntry; unit < ((uint64_t)entry + 1) * A.unitsPerEntry; unit++)
+      {
+         NfcApcmBase b;
+
+         b.record = carry.kept;
+         b.prevOffset = carry.last;
+         b.prevSample = carry.sample;
+         b.pad = 0;
+         A.bases[unit] = b;
+         carry = nfc_apcm_merge(carry, A.parts[unit]);
+      }
+
+      nfc_apcm_finish(A, entry, carry);
+   }
+}
+
+void nfc_apcm_encode_kernel(NfcApcmArgs A)
+{
+   static uint32_t stage[NfcApcmShape::kStageDwords];
+
+   for (uint64_t unit = 0; unit < A.units; unit++)
+   {
+      const uint32_t kept = A.parts[unit].kept;
+
+      if (!kept)
+         continue;
+
+      const NfcApcmBase b = A.bases[unit];
+      uint32_t buffer, begin, end, position, first, last, lead;
+
+      nfc_apcm_unit(A, unit, buffer, begin, end, position);
+      nfc_apcm_window(A, b.record, kept, first, last, lead);
+
+      const NfcApcmPair *row = nfc_apcm_row(A, buffer);
+      uint32_t beforeOffset = b.prevOffset, done = 0;
+      int32_t beforeSample = b.prevSample;
+
+      for (uint32_t i = begin; i < end && first + done < last; i++)
+      {
+         const NfcApcmPoint p = nfc_apcm_point(A, row, position, i);
+
+         if (!p.keep)
+            continue;
+
+         nfc_apcm_stage(stage, lead, done++, nfc_apcm_record(p, beforeOffset, beforeSample));
+         beforeOffset = p.offset;
+         beforeSample = p.sample;
+      }
+
+      for (uint32_t lane = 0; lane < 64 && last > first; lane++)
+         nfc_apcm_flush(nfc_apcm_window_at(A, buffer / A.buffersPerEntry, first, lead), stage, lead, 3u * (last - first), lane);
+   }
+}
 #else
+__global__ void nfc_apcm_count_kernel(NfcApcmArgs A);
+__global__ void nfc_apcm_scan_kernel(NfcApcmArgs A);
+__global__ void nfc_apcm_encode_kernel(NfcApcmArgs A);
 __global__ void nfc_tap_reduce_kernel(NfcTapReduceArgs A);
 __global__ void nfc_tap_reduce_finish_kernel(NfcTapReduceArgs A);
 __global__ void nfc_tap_walk_kernel(NfcTapArgs A, NfcConfig cfg);
@@ -779,6 +869,10 @@ struct nfcgpu_ctx
    /* nfcgpu_signal_tap_reduce: the planes of a slab, the partials of its units and the flag word (device), grown on demand, kept */
    void *tapReduceScratch = nullptr;
    size_t tapReduceScratchBytes = 0;
+
+   /* nfcgpu_apcm_encode: the parts and the bases of the units and the flag word (device), grown on demand, kept */
+   void *apcmScratch = nullptr;
+   size_t apcmScratchBytes = 0;
 };
 
 namespace {
@@ -3758,6 +3852,8 @@ int nfcgpu_shutdown(nfcgpu_ctx *ctx)
       (void)hipHostFree(ctx->tapCount);
    if (ctx->tapReduceScratch)
       (void)hipFree(ctx->tapReduceScratch);
+   if (ctx->apcmScratch)
+      (void)hipFree(ctx->apcmScratch);
    for (nfcgpu_ctx::StageSlot &slot: ctx->stage)
    {
       if (slot.d)
@@ -5537,6 +5633,217 @@ int nfcgpu_signal_tap_reduce(nfcgpu_ctx *ctx, const void *in, uint64_t inPitch, 
 
    if (*(const uint32_t *)(down->h + flagAt))
       return fail(ctx, NFCGPU_EINVAL, "tap reduce: a range in device memory is not inside the buffers or its reserved field is not zero; its records are empty");
+
+   return NFCGPU_OK;
+}
+
+/* ---- nfcgpu_apcm_encode: the resampler's control points as the APCM entries of a trace file (nfc_apcm.hpp) ---- */
+
+static_assert(sizeof(nfcgpu_apcm_info) == sizeof(NfcApcmInfo) && sizeof(NfcApcmInfo) == 16, "an APCM result record is 16 bytes");
+static_assert(sizeof(nfcgpu_apcm_params) == 56 && sizeof(NfcApcmPair) == 8 && sizeof(NfcApcmPart) == 24 && sizeof(NfcApcmBase) == 16, "APCM structures");
+
+constexpr uint64_t kApcmBlocks = 16384;   /* of four waves: the rest of the units by stride */
+
+uint64_t nfcgpu_apcm_bound(uint64_t totalPairs)
+{
+   return NFC_APCM_HEADER_BYTES + 3u * totalPairs;
+}
+
+int nfcgpu_apcm_encode(nfcgpu_ctx *ctx, const float *pairs, uint64_t pairsPitch, const uint32_t *counts, uint32_t nBuffers, uint32_t capacityPairs,
+                       const nfcgpu_apcm_params *params, void *out, uint64_t outPitch, uint64_t capacityBytes, nfcgpu_apcm_info *info, uint32_t location)
+{
+   SETTLE_FIRST(ctx);
+
+   if (!ctx)
+      return NFCGPU_EINVAL;
+   if (!params)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: params is NULL");
+   if (params->reserved0 | params->reserved[0] | params->reserved[1] | params->reserved[2] | params->reserved[3])
+      return fail(ctx, NFCGPU_EINVAL, "apcm: reserved fields of params are not zero");
+   if (location != NFCGPU_LOC_HOST && location != NFCGPU_LOC_DEVICE)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: unknown location");
+   if (params->sample_rate == 0)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: sample rate 0");
+
+   const uint32_t G = params->buffers_per_entry;
+
+   if (G == 0 || nBuffers % G != 0)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: buffers_per_entry is 0 or does not divide n_buffers");
+   if ((uint64_t)params->first_position + (uint64_t)G * params->buffer_samples > 0xFFFFFFFFull)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: the position of a buffer's end is not below 2^32");
+
+   const uint32_t nEntries = nBuffers / G;
+
+   if ((uint64_t)params->first_stream_id + nEntries > 0x100000000ull)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: a stream id is not below 2^32");
+
+   /* the range in samples: the reference's product and cast (TraceStorageTask.cpp:907-908); 0, 0 is everything */
+   const double start = (double)params->sample_rate * params->range_start, stop = (double)params->sample_rate * params->range_end;
+
+   if (!(params->range_start >= 0.0) || !(params->range_end >= params->range_start) || !(stop < 4294967296.0))
+      return fail(ctx, NFCGPU_EINVAL, "apcm: range_start and range_end are not 0 <= start <= end with sample_rate * end below 2^32");
+
+   const bool everything = params->range_start == 0.0 && params->range_end == 0.0;
+
+   if (((uintptr_t)pairs & 7) || (pairsPitch & 7) || pairsPitch < (uint64_t)capacityPairs * 8)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: pairs or pairs_pitch_bytes is not 8-byte aligned, or the pitch is smaller than capacity_pairs pairs");
+   if (((uintptr_t)counts & 3) || ((uintptr_t)info & 3))
+      return fail(ctx, NFCGPU_EINVAL, "apcm: counts or info is not 4-byte aligned");
+   if (((uintptr_t)out & 3) || (outPitch & 3))
+      return fail(ctx, NFCGPU_EINVAL, "apcm: out or out_pitch_bytes is not a multiple of 4");
+   if (capacityBytes < NFC_APCM_HEADER_BYTES || outPitch < capacityBytes)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: capacity_bytes is below the 32 bytes of a header or above out_pitch_bytes");
+   if ((uint64_t)G * capacityPairs > (0xFFFFFFFFull - NFC_APCM_HEADER_BYTES) / 3)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: the pairs of an entry (buffers_per_entry * capacity_pairs) need 4 GiB or more");
+
+   if (nBuffers == 0)
+      return NFCGPU_OK;
+
+   if (!pairs || !counts || !out || !info)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: pairs, counts, out or info is NULL");
+
+   const bool host = location == NFCGPU_LOC_HOST;
+
+   if (host)
+   {
+      for (uint32_t b = 0; b < nBuffers; b++)
+      {
+         if (counts[b] > capacityPairs)
+         {
+            const std::string what = "apcm: the count of buffer " + std::to_string(b) + " is above capacity_pairs";
+            return fail(ctx, NFCGPU_EINVAL, what.c_str());
+         }
+      }
+   }
+
+   HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+   NfcApcmArgs A;
+   std::memset(&A, 0, sizeof(A));
+
+   A.chunksPerBuffer = std::max<uint32_t>((uint32_t)(((uint64_t)capacityPairs + NfcApcmShape::kChunk - 1) / NfcApcmShape::kChunk), 1u);
+   A.units = (uint64_t)nBuffers * A.chunksPerBuffer;
+   A.unitsPerEntry = (uint64_t)G * A.chunksPerBuffer;
+   A.nBuffers = nBuffers;
+   A.nEntries = nEntries;
+   A.capacityPairs = capacityPairs;
+   A.buffersPerEntry = G;
+   A.bufferSamples = params->buffer_samples;
+   A.firstPosition = params->first_position;
+   A.firstStreamId = params->first_stream_id;
+   A.sampleRate = params->sample_rate;
+   A.sampleStart = everything ? 0u : (uint32_t)start;
+   A.sampleEnd = everything ? 0xFFFFFFFFu : (uint32_t)stop;
+   A.maxRecords = (uint32_t)std::min<uint64_t>((capacityBytes - NFC_APCM_HEADER_BYTES) / 3, 0xFFFFFFFFull);
+
+   /* scratch the context keeps: the flag word, the parts, the bases */
+   const size_t partsAt = 16, basesAt = partsAt + (size_t)A.units * sizeof(NfcApcmPart), need = basesAt + (size_t)A.units * sizeof(NfcApcmBase);
+
+   if (need > ctx->apcmScratchBytes)
+   {
+      if (ctx->apcmScratch)
+         (void)hipFree(ctx->apcmScratch);
+      ctx->apcmScratch = nullptr;
+      ctx->apcmScratchBytes = 0;
+      if (hipMalloc(&ctx->apcmScratch, need) != hipSuccess)
+         return fail(ctx, NFCGPU_ENOMEM, "apcm: scratch for the units could not be allocated");
+      ctx->apcmScratchBytes = need;
+   }
+
+   A.flag = (uint32_t *)ctx->apcmScratch;
+   A.parts = (NfcApcmPart *)((uint8_t *)ctx->apcmScratch + partsAt);
+   A.bases = (NfcApcmBase *)((uint8_t *)ctx->apcmScratch + basesAt);
+
+   /* host memory: one temporary device block - the rows packed to capacity_pairs, the counts, the entries, the results (this
+    * entry point is not on the streaming path) */
+   const size_t rowBytes = (size_t)capacityPairs * 8, entryPitch = (size_t)((capacityBytes + 3) & ~(uint64_t)3);
+   const size_t countsAt = rowBytes * nBuffers, entriesAt = (countsAt + (size_t)nBuffers * 4 + 15) & ~(size_t)15;
+   const size_t infoAt = entriesAt + entryPitch * nEntries, blockBytes = infoAt + (size_t)nEntries * sizeof(NfcApcmInfo);
+   uint8_t *block = nullptr;
+
+   struct Release
+   {
+      uint8_t **block;
+      ~Release()
+      {
+         if (*block)
+            (void)hipFree(*block);
+      }
+   } release {&block};
+
+   ctx->inflight = true;
+
+   if (host)
+   {
+      if (hipMalloc((void **)&block, blockBytes) != hipSuccess)
+         return fail(ctx, NFCGPU_ENOMEM, "apcm: device memory for host rows could not be allocated");
+
+      std::vector<uint8_t> up(entriesAt, 0);
+
+      for (uint32_t b = 0; b < nBuffers; b++)
+         std::memcpy(up.data() + rowBytes * b, (const uint8_t *)pairs + (size_t)pairsPitch * b, (size_t)counts[b] * 8);
+      std::memcpy(up.data() + countsAt, counts, (size_t)nBuffers * 4);
+
+      HIP_TRY(ctx, hipMemcpy(block, up.data(), entriesAt, hipMemcpyHostToDevice));
+
+      A.pairs = block;
+      A.pairsPitch = rowBytes;
+      A.counts = (const uint32_t *)(block + countsAt);
+      A.out = block + entriesAt;
+      A.outPitch = entryPitch;
+      A.info = (NfcApcmInfo *)(block + infoAt);
+   }
+   else
+   {
+      A.pairs = (const uint8_t *)pairs;
+      A.pairsPitch = pairsPitch;
+      A.counts = counts;
+      A.out = (uint8_t *)out;
+      A.outPitch = outPitch;
+      A.info = (NfcApcmInfo *)info;
+   }
+
+   HIP_TRY(ctx, hipMemsetAsync(A.flag, 0, 16, ctx->stream));
+
+   const uint32_t unitBlocks = (uint32_t)std::min<uint64_t>((A.units + NfcApcmShape::kWaves - 1) / NfcApcmShape::kWaves, kApcmBlocks);
+
+   hipLaunchKernelGGL(nfc_apcm_count_kernel, dim3(unitBlocks), dim3(64 * NfcApcmShape::kWaves), 0, ctx->stream, A);
+   HIP_TRY(ctx, hipGetLastError());
+   hipLaunchKernelGGL(nfc_apcm_scan_kernel, dim3(std::min<uint32_t>(nEntries, 65536u)), dim3(64), 0, ctx->stream, A);
+   HIP_TRY(ctx, hipGetLastError());
+   hipLaunchKernelGGL(nfc_apcm_encode_kernel, dim3(unitBlocks), dim3(64 * NfcApcmShape::kWaves), 0, ctx->stream, A);
+   HIP_TRY(ctx, hipGetLastError());
+
+   /* the results as the host sees them: what the call returns depends on them */
+   std::vector<NfcApcmInfo> results(nEntries);
+   uint32_t flag = 0;
+
+   HIP_TRY(ctx, hipMemcpyAsync(results.data(), A.info, (size_t)nEntries * sizeof(NfcApcmInfo), hipMemcpyDeviceToHost, ctx->stream));
+   HIP_TRY(ctx, hipMemcpyAsync(&flag, A.flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+   bool overflow = false;
+
+   for (uint32_t e = 0; e < nEntries; e++)
+      overflow = overflow || results[e].records > A.maxRecords;
+
+   if (host)
+   {
+      /* an entry's bytes and no others: what lies behind them in the caller's pitch is left alone */
+      std::vector<uint8_t> down(entryPitch * nEntries);
+
+      HIP_TRY(ctx, hipMemcpy(down.data(), A.out, down.size(), hipMemcpyDeviceToHost));
+
+      for (uint32_t e = 0; e < nEntries; e++)
+         std::memcpy((uint8_t *)out + (size_t)outPitch * e, down.data() + entryPitch * e,
+                     NFC_APCM_HEADER_BYTES + 3u * (size_t)std::min(results[e].records, A.maxRecords));
+      std::memcpy(info, results.data(), (size_t)nEntries * sizeof(NfcApcmInfo));
+   }
+
+   if (flag)
+      return fail(ctx, NFCGPU_EINVAL, "apcm: a count in device memory is above capacity_pairs; capacity_pairs pairs of that buffer were taken");
+   if (overflow)
+      return fail(ctx, NFCGPU_EOVERFLOW, "apcm: an entry needs more than capacity_bytes: its info says how many");
 
    return NFCGPU_OK;
 }

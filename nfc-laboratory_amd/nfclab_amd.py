@@ -33,6 +33,7 @@ TAP_STATE_DTYPE = np.dtype([("clock", np.uint32), ("pulse_filter", np.uint32), (
                             ("deviation", np.float32), ("average", np.float32), ("reserved", np.uint32, (2,))])
 
 # nfcgpu_signal_tap_reduce: one nfcgpu_tap_range per range, one nfcgpu_tap_stat per range and selected channel
+APCM_INFO_DTYPE = np.dtype([("bytes", np.uint32), ("records", np.uint32), ("wrapped", np.uint32), ("reserved", np.uint32)])
 TAP_RANGE_DTYPE = np.dtype([("buffer", np.uint32), ("first", np.uint32), ("count", np.uint32), ("reserved", np.uint32)])
 TAP_STAT_DTYPE = np.dtype([("min", np.float32), ("max", np.float32), ("mean", np.float32), ("valid", np.uint32), ("argmin", np.uint32),
                            ("argmax", np.uint32), ("reserved", np.uint32, (2,))])
@@ -157,6 +158,20 @@ class TapReduceParams(ctypes.Structure):
     ]
 
 
+class ApcmParams(ctypes.Structure):
+    _fields_ = [
+        ("sample_rate", ctypes.c_uint32),
+        ("buffers_per_entry", ctypes.c_uint32),
+        ("buffer_samples", ctypes.c_uint32),
+        ("first_stream_id", ctypes.c_uint32),
+        ("first_position", ctypes.c_uint32),
+        ("reserved0", ctypes.c_uint32),
+        ("range_start", ctypes.c_double),
+        ("range_end", ctypes.c_double),
+        ("reserved", ctypes.c_uint32 * 4),
+    ]
+
+
 # the reference's window names (FourierProcessTask.cpp:121-143; see include/nfcgpu.h for what they compute)
 WINDOWS = {"none": 0, "hamming": 1, "hann": 2}
 
@@ -216,6 +231,10 @@ def load_library(path=LIB_PATH):
     lib.nfcgpu_signal_tap.argtypes = [vp, vp, u64, u32, u32, u32, u32, P(TapParams), vp, vp, u64, u64, vp, P(TapReport), u32]
     lib.nfcgpu_stream_tap_state.argtypes = [vp, u32, vp]
     lib.nfcgpu_signal_tap_reduce.argtypes = [vp, vp, u64, u32, u32, u32, u32, P(TapParams), P(TapReduceParams), vp, vp, u32, vp, vp, P(TapReport), u32]
+    lib.nfcgpu_apcm_bound.argtypes = [u64]
+    lib.nfcgpu_apcm_bound.restype = u64
+    lib.nfcgpu_apcm_encode.argtypes = [vp, vp, u64, vp, u32, u32, P(ApcmParams), vp, u64, u64, vp, u32]
+    lib.nfcgpu_trace_write_signal.argtypes = [ctypes.c_char_p, vp, u32, ctypes.c_int64, ctypes.c_double, ctypes.c_double, P(u32), P(vp), P(u64), u32]
     lib.nfcgpu_wav_write.argtypes = [ctypes.c_char_p, vp, u64, u32, u32, u32, vp]
     lib.nfcgpu_wav_append.argtypes = [ctypes.c_char_p, vp, u64]
     lib.nfcgpu_flush.argtypes = [vp, u32]
@@ -282,6 +301,34 @@ def wav_append(path, pcm):
     if channels == 0 or pcm.size % channels:
         raise NfcGpuError(-1, "not a capture file, or samples that do not fill its channels")
     _wav_check(load_library().nfcgpu_wav_append(os.fsencode(path), pcm.ctypes.data, pcm.size // channels))
+
+
+def as_frames(frames):
+    """A ctypes array of Frame records of such an array or of the tuples NfcGpu.poll returns."""
+    if isinstance(frames, ctypes.Array):
+        return frames
+    out = (Frame * max(len(frames), 1))()
+    for f, t in zip(out, frames):
+        f.tech_type, f.frame_type, f.frame_flags, f.frame_phase, f.frame_rate, f.sample_start, f.sample_end, f.sample_rate = (int(v) for v in t[:8])
+        payload = bytes(t[8])
+        f.length = len(payload)
+        ctypes.memmove(f.data, payload, min(len(payload), 512))
+    return out
+
+
+def trace_write_signal(path, frames, entries, stream_time=0, range_start=0.0, range_end=0.0):
+    """A .trz with frame.json and one radio-<id>.apcm per APCM entry (nfcgpu_trace_write_signal): frames as NfcGpu.poll returns
+    them (or a ctypes array of Frame), entries a list of bytes-like APCM entries as apcm_encode returns them. range_start /
+    range_end select and shift the frames as nfcgpu_trace_write_frames does; the entries go in as they are. No context and no
+    device. Returns the number of frames written."""
+    records = as_frames(frames)
+    held = [np.frombuffer(bytes(e), dtype=np.uint8) for e in entries]
+    pointers = (ctypes.c_void_p * max(len(held), 1))(*[h.ctypes.data for h in held])
+    sizes = (ctypes.c_uint64 * max(len(held), 1))(*[h.size for h in held])
+    n = ctypes.c_uint32()
+    _wav_check(load_library().nfcgpu_trace_write_signal(os.fsencode(path), ctypes.cast(records, ctypes.c_void_p), len(frames), int(stream_time),
+                                                        range_start, range_end, ctypes.byref(n), pointers, sizes, len(held)))
+    return int(n.value)
 
 
 def as_tap_ranges(ranges):
@@ -569,6 +616,60 @@ class NfcGpu:
         self._check(self.lib.nfcgpu_signal_tap_reduce(self.ctx, in_ptr, in_pitch_bytes, n_buffers, n_samples, stride, fmt, ctypes.byref(p), ctypes.byref(q),
                                                       state_in_ptr, ranges_ptr, n_ranges, out_ptr, state_out_ptr, ctypes.byref(report), LOC_DEVICE))
         return report
+
+    def apcm_encode(self, points, sample_rate, buffers_per_entry=1, buffer_samples=0, first_stream_id=0, first_position=0, range_start=0.0,
+                    range_end=0.0, with_info=False):
+        """The control points of consecutive buffers (a list of (pairs, 2) float32 arrays as resample_radio returns them; host
+        memory) as APCM entries (nfcgpu_apcm_encode): buffers_per_entry buffers make an entry, buffer j of an entry stands at the
+        stream position first_position + j * buffer_samples, entry e carries the id first_stream_id + e. Returns a list of bytes,
+        one per entry; with_info: (entries, APCM_INFO_DTYPE [n_entries])."""
+        points = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2) for p in points]
+        nb = len(points)
+        assert buffers_per_entry and nb % buffers_per_entry == 0
+        n_entries = nb // buffers_per_entry
+        counts = np.array([p.shape[0] for p in points], dtype=np.uint32)
+        cap = int(counts.max()) if nb else 0
+        rows = np.zeros((max(nb, 1), 2 * max(cap, 1)), dtype=np.float32)
+        for b, p in enumerate(points):
+            rows[b, :2 * p.shape[0]] = p.reshape(-1)
+        most = max([int(counts[e * buffers_per_entry:(e + 1) * buffers_per_entry].sum()) for e in range(n_entries)], default=0)
+        pitch = (int(self.lib.nfcgpu_apcm_bound(most)) + 3) & ~3
+        out = np.zeros((max(n_entries, 1), pitch), dtype=np.uint8)
+        info = np.zeros(max(n_entries, 1), dtype=APCM_INFO_DTYPE)
+        p = ApcmParams(sample_rate, buffers_per_entry, buffer_samples, first_stream_id, first_position, 0, range_start, range_end)
+        self._check(self.lib.nfcgpu_apcm_encode(self.ctx, rows.ctypes.data, rows.shape[1] * 4, counts.ctypes.data, nb, cap, ctypes.byref(p),
+                                                out.ctypes.data, pitch, pitch, info.ctypes.data, LOC_HOST))
+        entries = [out[e, :int(info["bytes"][e])].tobytes() for e in range(n_entries)]
+        return (entries, info[:n_entries]) if with_info else entries
+
+    def apcm_encode_device(self, pairs_ptr, pairs_pitch_bytes, counts_ptr, n_buffers, capacity_pairs, sample_rate, out_ptr, out_pitch_bytes,
+                           capacity_bytes, info_ptr, buffers_per_entry=1, buffer_samples=0, first_stream_id=0, first_position=0, range_start=0.0,
+                           range_end=0.0):
+        """Same with device pointers: the rows and counts nfcgpu_resample_radio left in HBM, the entries and their APCM_INFO_DTYPE
+        records written there. An entry that does not fit raises NfcGpuError (NFCGPU_EOVERFLOW), a count above capacity_pairs
+        NFCGPU_EINVAL, with every entry complete as far as it goes."""
+        p = ApcmParams(sample_rate, buffers_per_entry, buffer_samples, first_stream_id, first_position, 0, range_start, range_end)
+        self._check(self.lib.nfcgpu_apcm_encode(self.ctx, pairs_ptr, pairs_pitch_bytes, counts_ptr, n_buffers, capacity_pairs, ctypes.byref(p), out_ptr,
+                                                out_pitch_bytes, capacity_bytes, info_ptr, LOC_DEVICE))
+
+    def trace_write_capture(self, path, samples, sample_rate, frames=(), buffer_samples=65536, stride=1, fmt=FMT_F32, stream_id=0, stream_time=0,
+                            range_start=0.0, range_end=0.0):
+        """A stream's capture and its frames as a .trz whose signal view is filled: the samples (1-D, host memory; the format is
+        what `fmt` and `stride` say) are cut into buffers of buffer_samples (the last one may be shorter, at least 25 samples),
+        resampled (resample_radio), encoded as one APCM entry (apcm_encode) and written with the frames (trace_write_signal).
+        range_start / range_end apply to the signal and to the frames alike. Returns (frames written, points stored)."""
+        samples = np.ascontiguousarray(samples, dtype=np.int16 if fmt == FMT_I16 else np.float32).reshape(-1)
+        n = samples.size // stride
+        whole = n // buffer_samples
+        points = []
+        if whole:
+            points += self.resample_radio(samples[:whole * buffer_samples * stride].reshape(whole, -1), stride=stride, fmt=fmt)
+        if n - whole * buffer_samples >= 25:
+            points += self.resample_radio(samples[whole * buffer_samples * stride:n * stride].reshape(1, -1), stride=stride, fmt=fmt)
+        entries, info = self.apcm_encode(points, sample_rate, buffers_per_entry=max(len(points), 1), buffer_samples=buffer_samples,
+                                         first_stream_id=stream_id, range_start=range_start, range_end=range_end, with_info=True) if points else ([], [])
+        written = trace_write_signal(path, frames, entries, stream_time, range_start, range_end)
+        return written, int(info["records"][0]) if points else 0
 
     def stream_tap_state(self, stream):
         """TAP_STATE_DTYPE [1]: the front-end state the stream's next buffer will start from (nfcgpu_stream_tap_state)."""
